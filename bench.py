@@ -6,12 +6,25 @@ Workload (BASELINE.json configs[1]): the 6.17 M-parameter fp32 model, batch of 3
 (temporal binding, 8 SSM blocks, hierarchical global context, CTC head) + argmax + greedy
 collapse, on audio already resident in HBM, replayed as HIP graphs.
 
-Multi-GPU: one process per GPU.  `python bench.py --gpus N` without WORLD_SIZE starts
-`python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (before
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline
+figure needs, in this process: it builds the model and the graphs (schedule tuning included),
+warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given and
+prints the result line (metric, value, unit, ms_per_step, ...).  Everything else described
+below -- the roofline and per-kernel figures, the token checks against the reference and an
+eager pass, the machine record, the CPU baseline, the serving leg, and for one GPU the launch
+through torch.distributed.run -- runs only with --full.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step as float32
+arrays: DIR/tokens.npy (batch, L; positions at and past a clip's length are -1) and
+DIR/lengths.npy (batch,); with more than one rank, tokens_rank<r>.npy and lengths_rank<r>.npy.
+Weights and audio are seeded, so two runs with the same arguments have identical inputs.
+
+Multi-GPU: one process per GPU.  `python bench.py --gpus N` (N > 1, or --full) without WORLD_SIZE
+starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (before
 anything touches the GPU) and exits with its code.  Each rank transcribes its own 32 clips
 (utterance sharding, no data-path collective; weak scaling); a barrier + synchronize brackets
 the K timed steps and the max time over ranks is used -- barriers and max in a gloo process
-group on the host (an RCCL communicator's mere presence slowed the replays 2.2 %).  A second
+group on the host (an RCCL communicator's mere presence slowed the replays 2.2 %).  With --full a second
 timed leg ("with_scatter") runs the serving form over an RCCL ("nccl") group joined after the
 first: rank 0 holds the whole (N*32, S) batch in HBM, each step scatters the shards over RCCL
 (xGMI) straight into every rank's graph input, replays, and gathers the int32 tokens back to
@@ -19,6 +32,8 @@ rank 0 (velocity_asr.distributed.transcribe_sharded).
 
 Prints ONE JSON line (rank 0):
   value         = RTFx = audio seconds transcribed by all ranks / wall seconds (resident inputs)
+  ms_per_step   = wall milliseconds per timed step (the K steps between two synchronizes / K)
+with --full also, among others:
   roofline      = the dominant kernel measured live with HIP events (eager replay of the same
                   steps on the launch stream) against the MI355X peak; flat scalar fields add
                   the scan's VALU roof, the HBM ceiling its arithmetic allows, and the GEMM
@@ -65,8 +80,15 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=10.0, help="clip length")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: roofline and "
+                         "per-kernel timings, the token checks against the reference and an eager pass (they "
+                         "decide the exit code), the machine record, the CPU baseline, the serving leg; with "
+                         "--gpus 1 the rank is started through torch.distributed.run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tokens and lengths of the last timed step to DIR as float32 .npy files")
     ap.add_argument("--eager", action="store_true", help="time eager launches instead of the HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-scatter", action="store_true", help="skip the scatter/gather serving leg")
     ap.add_argument("--serving-timeout", type=float, default=120.0,
                     help="seconds an RCCL collective of the serving leg may take before it fails that leg "
@@ -74,7 +96,7 @@ def parse_args(argv=None):
     ap.add_argument("--gloo-timeout", type=float, default=900.0, help="seconds a host-side barrier may wait")
     ap.add_argument("--inproc", action="store_true",
                     help="run a single rank in this process instead of through torch.distributed.run")
-    ap.add_argument("--roofline-steps", type=int, default=3)
+    ap.add_argument("--roofline-steps", type=int, default=3, help="with --full: eager steps of the roofline pass")
     ap.add_argument("--streams", type=int, default=0,
                     help="utterance groups replayed as separate HIP graphs on concurrent streams (the scan of one "
                          "group overlaps the GEMMs of the other; results are bitwise those of one graph); "
@@ -640,9 +662,10 @@ def run(args):
             dist.init_process_group("gloo", timeout=timedelta(seconds=args.gloo_timeout))
             dist.barrier()
 
+    eager_out = []
     if args.eager:
         def step():
-            return audio_to_token_ids(model, audio)
+            eager_out[:] = audio_to_token_ids(model, audio)
         tr = None
     else:
         if streams:
@@ -662,13 +685,22 @@ def run(args):
     # the warm-up's last replay is checked against the reference too, after the timed steps: its
     # tokens are copied on the device here (no host work between the warm-up and the timed steps --
     # an idle device starts the next steps up to 25 % slower, profiles/r05j/step_course.txt)
-    warm_copy = tuple(t.clone() for t in tr.collect()) if tr is not None else None
+    warm_copy = tuple(t.clone() for t in tr.collect()) if tr is not None and args.full else None
     step_ms = []
     elapsed = timed(step, args.steps, world, dev, per_step=step_ms)
-    from velocity_asr.ops import probe_clock
-    machine = probe_clock(dev)  # right after the timed steps: the clock they left, the XCD dispatch order
+    if args.full:
+        from velocity_asr.ops import probe_clock
+        machine = probe_clock(dev)  # right after the timed steps: the clock they left, the XCD dispatch order
     if tr is not None and hasattr(tr, "release_candidates"):
         tr.release_candidates()  # the schedules not chosen (kept until now: freeing them stalls the device)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *(tr.collect() if tr is not None else eager_out), rank, world)
+    if not args.full:  # a plain run ends here, with the headline line
+        line = None
+        if rank == 0:
+            line = headline(args, world, distributed, B, S_len, streams, schedule, elapsed, step_ms)
+        finish(line, rank, world, distributed, None, lambda: 0, args.serving_timeout)
+        return 0
     warm_golden = None
     if warm_copy is not None:
         wc = torch.tensor(golden_check(*warm_copy, args, rank), dtype=torch.float64)
@@ -731,12 +763,51 @@ def run(args):
     return rc
 
 
-def result_line(args, world, distributed, B, S_len, streams, schedule, elapsed, step_ms, machine, rf, iso, iso_full,
-                graph_match, golden, warm_golden, golden_eager, csum):
-    """Rank 0's JSON line for the resident leg (the contract's fields, the roofline, the checks)."""
+def dump_outputs(path, toks, lens, rank, world):
+    """--dump-outputs: what the timed path returned in its last step, as float32 .npy files in
+    `path` (token ids and lengths are small integers, exact in float32).  Positions at and past a
+    clip's length hold no result and are written as -1."""
+    os.makedirs(path, exist_ok=True)
+    t, n = toks.cpu().numpy(), lens.cpu().numpy()
+    t = np.where(np.arange(t.shape[1])[None, :] < n[:, None], t, -1)
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(path, f"tokens{tag}.npy"), t.astype(np.float32))
+    np.save(os.path.join(path, f"lengths{tag}.npy"), n.astype(np.float32))
+
+
+def headline(args, world, distributed, B, S_len, streams, schedule, elapsed, step_ms):
+    """Rank 0's JSON line of a plain run: the contract's fields from the timed steps alone."""
     audio_sec = world * B * args.seconds * args.steps
     frames = world * B * (S_len // 160 + 1) * args.steps
-    ms_per_step = elapsed / args.steps * 1e3
+    return {
+        "metric": METRIC,
+        "value": round(audio_sec / elapsed, 2),
+        "unit": "audio-sec/sec (RTFx)",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16" if args.bf16 else "f32",
+        "data": "synthetic: N(0, 0.1) 16 kHz clips; seeded random-init weights (velocity_asr.synthetic)",
+        "full": bool(args.full),
+        "config": {"workload": f"{B} x {args.seconds:g} s clips per GPU, audio->mel->forward->CTC greedy tokens "
+                               f"(BASELINE configs[{4 if args.int8 else 2 if args.bf16 else 1}]"
+                               f"{', INT8 fake-quant' if args.int8 else ''}"
+                               f"{f', HIP graph x{streams} streams' if not args.eager else ', eager'})",
+                   "global_batch": world * B, "clip_seconds": args.seconds, "schedule": schedule,
+                   "parallelism": _parallelism(world, None) if distributed else "single process"},
+        "frames_per_sec": round(frames / elapsed, 1),
+        "step_ms_device": step_stats(step_ms),
+    }
+
+
+def result_line(args, world, distributed, B, S_len, streams, schedule, elapsed, step_ms, machine, rf, iso, iso_full,
+                graph_match, golden, warm_golden, golden_eager, csum):
+    """Rank 0's JSON line of a --full run for the resident leg (the headline fields, the roofline,
+    the checks)."""
     sc, gm = rf.get("scan"), rf["gemm"]
     # GEMM family: split-bf16 ("x3") products = six bf16 MFMA products per fp32 multiply-add
     x3 = not args.bf16
@@ -806,28 +877,9 @@ def result_line(args, world, distributed, B, S_len, streams, schedule, elapsed, 
         t = t.get("%d@%d" % (sc["B"] * (sc["Di"] // 16) * 256, sc["L"]))
     if isinstance(t, (int, float)):
         roof["traffic"] = t
-    line = {
-        "metric": METRIC,
-        "value": round(audio_sec / elapsed, 2),
-        "unit": "audio-sec/sec (RTFx)",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16" if args.bf16 else "f32",
-        "data": "synthetic: N(0, 0.1) 16 kHz clips; seeded random-init weights (velocity_asr.synthetic)",
-        "config": {"workload": f"{B} x {args.seconds:g} s clips per GPU, audio->mel->forward->CTC greedy tokens "
-                               f"(BASELINE configs[{4 if args.int8 else 2 if args.bf16 else 1}]"
-                               f"{', INT8 fake-quant' if args.int8 else ''}"
-                               f"{f', HIP graph x{streams} streams' if not args.eager else ', eager'})",
-                   "global_batch": world * B, "clip_seconds": args.seconds, "schedule": schedule,
-                   "parallelism": _parallelism(world, None) if distributed else "single process"},
-        "frames_per_sec": round(frames / elapsed, 1),
+    line = headline(args, world, distributed, B, S_len, streams, schedule, elapsed, step_ms)
+    line.update({
         "machine": machine,
-        "step_ms_device": step_stats(step_ms),
         "roofline": roof,
         "with_scatter": None,
         "kernels": {
@@ -846,7 +898,7 @@ def result_line(args, world, distributed, B, S_len, streams, schedule, elapsed, 
         "tokens_vs_reference": golden,
         "warmup_tokens_vs_reference": warm_golden,
         "eager_tokens_vs_reference": golden_eager,
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
     return line
@@ -854,7 +906,9 @@ def result_line(args, world, distributed, B, S_len, streams, schedule, elapsed, 
 
 def main():
     args = parse_args()
-    if "WORLD_SIZE" not in os.environ and not args.inproc:
+    # a plain one-GPU run stays in this process; N > 1 ranks, and --full (whose serving leg joins
+    # an RCCL group), start through torch.distributed.run
+    if "WORLD_SIZE" not in os.environ and not args.inproc and (args.gpus != 1 or args.full):
         sys.exit(launch(args))
     if args.inproc and args.gpus != 1:
         log("bench.py: --inproc runs one rank; use --gpus 1")

@@ -60,6 +60,33 @@ def test_forced_mismatch_fails_the_run():
     assert bench.run_verdict(True, None, None, None) == (0, [])
 
 
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    toks, lens = _as_tensors([[3, 7, 7], [], [999]])
+    toks[1, :] = 55  # past a clip's length: no result, written as -1
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), toks, lens, rank=0, world=1)
+    assert sorted(os.listdir(out)) == ["lengths.npy", "tokens.npy"]
+    t, n = np.load(out / "tokens.npy"), np.load(out / "lengths.npy")
+    assert t.dtype == np.float32 and n.dtype == np.float32
+    assert t.tolist() == [[3, 7, 7], [-1, -1, -1], [999, -1, -1]] and n.tolist() == [3, 0, 1]
+    bench.dump_outputs(str(out), toks, lens, rank=1, world=2)
+    assert (out / "tokens_rank1.npy").exists() and (out / "lengths_rank1.npy").exists()
+
+
+def test_plain_run_is_the_default():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    step_ms = [2.0] * 7 + [dict(host_step_ms=[0.04] * 7, issue_ms=0.3)]
+    line = bench.headline(bench.parse_args(["--steps", "7"]), 1, False, 32, 160000, 1, None, 0.014, step_ms)
+    assert line["steps"] == 7 and line["ms_per_step"] == 2.0 and line["full"] is False
+    assert line["value"] == round(32 * 10.0 * 7 / 0.014, 2) and line["higher_is_better"] is True
+    assert line["unit"] == "audio-sec/sec (RTFx)" and line["dtype"] == "f32" and line["metric"] == bench.METRIC
+    for k in ("roofline", "cpu_baseline", "with_scatter", "tokens_vs_reference", "machine"):
+        assert k not in line
+
+
 def test_schedule_how_reflects_candidates():
     assert "single candidate" in bench.schedule_how({}, 1)
     h = bench.schedule_how({1: 2.1, 2: 2.2}, 1)

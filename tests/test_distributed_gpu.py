@@ -2,7 +2,7 @@
 
 Only one GPU is available to the tests, so the RCCL path runs at world size 1 in a child
 process (scatter from rank 0, HIP graphs, gather), and bench.py's launcher is exercised end
-to end with --gpus 1 (torch.distributed.run as a child, one rank).  The sharded form at world
+to end with --gpus 1 --full (torch.distributed.run as a child, one rank).  The sharded form at world
 size 2 (C3's partitioning: rank r transcribes its own slice of the batch) runs with both ranks
 on the one GPU over a gloo group (RCCL refuses two ranks on one device): real HIP steps,
 host-side scatter/gather.  The 8-GPU RCCL run is the driver's scaling bench."""
@@ -73,14 +73,14 @@ def test_rccl_sharded_transcription_world1_matches_reference():
 
 
 def test_bench_launcher_one_gpu():
-    """bench.py --gpus 1 goes through torch.distributed.run (child process), joins an RCCL
+    """bench.py --gpus 1 --full goes through torch.distributed.run (child process), joins an RCCL
     group, runs the resident and the scatter/gather legs and prints one JSON line."""
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--roofline-steps", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
-                       timeout=400, cwd=REPO)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--full", "--steps", "3",
+                        "--warmup", "1", "--roofline-steps", "1", "--no-cpu-baseline"], env=env, capture_output=True,
+                       text=True, timeout=400, cwd=REPO)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout  # ONE JSON line, no banners
@@ -92,6 +92,37 @@ def test_bench_launcher_one_gpu():
     assert d["with_scatter"]["rank0_tokens_match"] is True and d["with_scatter"]["value"] > 0
     for k in ("valu_frac", "hbm_ceiling_frac", "gemm_frac", "gemm_f32eq_frac"):
         assert k in d["roofline"], k
+
+
+def test_bench_plain_run_one_gpu(tmp_path):
+    """A plain bench.py --gpus 1 run stays in one process, times exactly --steps steps, prints one
+    JSON line with the headline fields only, and --dump-outputs writes the last timed step's tokens:
+    the reference's greedy lists for the bench's first 4 clips (tests/golden/fwd_fullbatch.npz)."""
+    import numpy as np
+    from conftest import golden
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "4", "--dump-outputs", str(out)], env=env, capture_output=True, text=True,
+                       timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(4 * 10.0 / (d["ms_per_step"] * 1e-3), rel=1e-2)
+    assert len(d["step_ms_device"]["device_ms"]) == 3
+    assert d["config"]["parallelism"] == "single process"
+    for k in ("roofline", "kernels", "cpu_baseline", "with_scatter", "tokens_vs_reference", "machine"):
+        assert k not in d, k
+    toks, lens = np.load(out / "tokens.npy"), np.load(out / "lengths.npy")
+    assert toks.dtype == np.float32 and lens.dtype == np.float32 and toks.shape[0] == 4 and lens.shape == (4,)
+    got = [toks[b, :int(lens[b])].astype(int).tolist() for b in range(4)]
+    assert got == json.loads(str(golden("fwd_fullbatch.npz")["greedy"]))["c2"][:4]
+    assert (toks[np.arange(toks.shape[1])[None, :] >= lens[:, None]] == -1).all()
 
 
 CHILD2 = r"""

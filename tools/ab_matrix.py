@@ -21,7 +21,7 @@ def main():
     for r in range(rounds):
         for name, env, args in variants:
             e = dict(os.environ, **env)
-            cmd = [sys.executable, "bench.py", "--no-cpu-baseline", "--no-scatter"] + args
+            cmd = [sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-scatter"] + args
             p = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=400)
             rec = dict(name=name, round=r, env=env, args=args, rc=p.returncode)
             if p.returncode == 0:

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 i=0
 for v in "$@"; do
   log=gpurun_out/ab_${VAR}_${v}_$i.log
-  env "$VAR=$v" timeout -k 10 200 python bench.py --no-cpu-baseline > "$log" 2>&1
+  env "$VAR=$v" timeout -k 10 200 python bench.py --full --no-cpu-baseline > "$log" 2>&1
   tail -n 1 "$log" | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -1,12 +1,14 @@
 #!/bin/bash
 # End-to-end bench of the default library and each variant in tools/_variants/ (VASR_LIB), interleaved twice.
+# Logs go to $OUT_DIR (default bench_out).
 set -euo pipefail
-mkdir -p gpurun_out
+OUT=${OUT_DIR:-bench_out}
+mkdir -p $OUT
 run() {
   local name=$1 lib=$2
-  if [ -n "$lib" ]; then VASR_LIB=$lib timeout -k 10 200 python bench.py --no-cpu-baseline > gpurun_out/bl_$name.log 2>&1
-  else timeout -k 10 200 python bench.py --no-cpu-baseline > gpurun_out/bl_$name.log 2>&1; fi
-  tail -n 1 gpurun_out/bl_$name.log | python3 -c "
+  if [ -n "$lib" ]; then VASR_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline > $OUT/bl_$name.log 2>&1
+  else timeout -k 10 200 python bench.py --full --no-cpu-baseline > $OUT/bl_$name.log 2>&1; fi
+  tail -n 1 $OUT/bl_$name.log | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['kernels']
 print('$name', d['value'], d['ms_per_step'], k['scan']['avg_launch_us'], k['gemm']['avg_launch_us'])"

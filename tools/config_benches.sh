@@ -6,7 +6,7 @@ set -euo pipefail
 TAG=${1:-r02}
 OUT=gpurun_out/cfg_$TAG
 mkdir -p $OUT
-run() { local name=$1; shift; timeout -k 10 300 python bench.py --inproc --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err; }
+run() { local name=$1; shift; timeout -k 10 300 python bench.py --full --inproc --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err; }
 run c2
 run c3_bf16 --bf16
 run c4_30s --seconds 30

@@ -11,7 +11,7 @@ for r in $(seq 1 $R); do
     for b in 16 32; do
       VASR_LIB=$lib timeout -k 10 60 python tools/scan_bench.py $b 501 384 64 2 200 2>/dev/null | sed "s/^/$n /" >> $OUT/scan.txt
     done
-    VASR_LIB=$lib timeout -k 10 200 python bench.py --no-cpu-baseline --no-scatter > $OUT/bench.$n.$r.json 2>/dev/null
+    VASR_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-scatter > $OUT/bench.$n.$r.json 2>/dev/null
     python -c "import json,sys;d=json.load(open('$OUT/bench.$n.$r.json'));print('$n',$r,d['value'],d['roofline']['avg_launch_us'])" >> $OUT/summary.txt
   done
 done

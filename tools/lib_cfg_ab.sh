@@ -9,7 +9,7 @@ for r in $(seq 1 $R); do
     name=${cfg%%:*}; args=${cfg#*:}
     for lib in "$@"; do
       n=$(basename $lib .so)
-      VASR_LIB=$lib timeout -k 10 200 python bench.py --inproc --no-cpu-baseline --no-scatter $args > $OUT/$name.$n.$r.json 2>/dev/null
+      VASR_LIB=$lib timeout -k 10 200 python bench.py --full --inproc --no-cpu-baseline --no-scatter $args > $OUT/$name.$n.$r.json 2>/dev/null
       python -c "import json;d=json.load(open('$OUT/$name.$n.$r.json'));print('$name $n r$r',d['value'],d['ms_per_step'],d['roofline']['avg_launch_us'],d.get('rank0_tokens_match_reference'))" >> $OUT/summary.txt
     done
   done

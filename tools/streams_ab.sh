@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   for cfg in "c2:" "c4:--seconds 30" "c3:--bf16"; do
     name=${cfg%%:*}; args=${cfg#*:}
     for s in 1 2; do
-      timeout -k 10 200 python bench.py --inproc --no-cpu-baseline --streams $s $args > $OUT/$name.s$s.$r.json 2>/dev/null
+      timeout -k 10 200 python bench.py --full --inproc --no-cpu-baseline --streams $s $args > $OUT/$name.s$s.$r.json 2>/dev/null
       python -c "import json;d=json.load(open('$OUT/$name.s$s.$r.json'));r=d['roofline'];print('$name s$s r$r',d['value'],d['ms_per_step'],r['frac'],r['avg_launch_us'])" >> $OUT/summary.txt
     done
   done
