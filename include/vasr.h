@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define VASR_ABI_VERSION 19
+#define VASR_ABI_VERSION 20
 
 #define VASR_OK 0
 #define VASR_EINVAL (-1)
@@ -442,6 +442,54 @@ int vasr_ctc_collapse_var(const int32_t* pred, int B, int L, const int32_t* fram
 int vasr_ctc_collapse_keys(const uint64_t* keys, int64_t ld, int slots, int B, int L, const int32_t* frames,
                            int blank, int collapse, int32_t* pred, int32_t* out_tokens, int32_t* out_len,
                            int32_t* out_start, int32_t* out_end, void* stream);
+
+/* ------------------------------------------------------------------ CTC loss and forced alignment
+ * Forward-only scoring of a KNOWN transcript (training.py:47-104: F.log_softmax + nn.CTCLoss as
+ * Trainer.eval_step, training.py:273-299, uses them for eval_loss), and the Viterbi form of the
+ * same lattice: per-token frame spans, the companion of ctc_greedy_decode_with_timestamps
+ * (decode.py:74-125), which only timestamps the model's own guess.  No gradients.
+ *
+ * Common arguments: targets (B, Smax) int32 (may be NULL if Smax == 0); frames[B] and tlen[B]
+ * device int32, clamped to [0, L] and [0, Smax]; rows t >= frames[b] and target slots
+ * j >= tlen[b] are neither read nor used.  1 <= L <= 8192 (VASR_EINVAL otherwise), Smax <= 2048
+ * (VASR_EUNSUPPORTED above).
+ *
+ * Stage 1, the only pass over the logits ((B, L, V), row stride ld_row >= V, utterance stride
+ * ld_utt, as vasr_ctc_beam_search; any V, any alignment): emis (B, L, Smax + 1) contiguous,
+ *   emis[b][t][0]     = logit[b,t,blank]         - lse[b,t]
+ *   emis[b][t][1 + j] = logit[b,t,targets[b][j]] - lse[b,t]      (j < tlen[b])
+ * with lse the fp32 max-subtracted log-sum-exp of the row; entries of padding rows and slots are
+ * left unwritten.  A target id outside [0, V) (within tlen[b]) is never used as an index: its
+ * emission is -inf, so that utterance scores as an infeasible target (nll +inf, align score -inf). */
+int vasr_ctc_emissions_f32(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                           const int32_t* targets, int Smax, const int32_t* frames, const int32_t* tlen,
+                           int blank, float* emis, void* stream);
+
+/* Stage 2a: out_nll[b] = -log p(targets[b] | logits[b]) over the extended label sequence of
+ * S' = 2 tlen + 1 states (blanks interleaved): a state is reached from s, s - 1, and from s - 2
+ * only when s is a non-blank that differs from state s - 2 (the recursion of
+ * torch.nn.functional.ctc_loss); nll = -logsumexp(alpha[T-1][S'-1], alpha[T-1][S'-2]), all in
+ * fp32 log space with the maximum subtracted.  An infeasible target gives +inf (zero_infinity is
+ * the caller's); tlen = 0 sums the blank emissions; frames = 0 gives 0 for tlen = 0, else +inf.
+ * One workgroup per utterance; each value depends on its own utterance only. */
+int vasr_ctc_loss_f32(const float* emis, int B, int L, int Smax, const int32_t* targets,
+                      const int32_t* frames, const int32_t* tlen, float* out_nll, void* stream);
+
+/* Stage 2b, the Viterbi form: the best path through the same lattice.
+ *   frame_state (B, L): the target index frame t emits, -1 for blank and for t >= frames[b];
+ *   out_start / out_end (B, Smax): first frame and one past the last frame of token j's run
+ *     (the convention of ctc_greedy_decode_with_timestamps), -1 for j >= tlen[b];
+ *   out_score[b]: the path's log-probability.
+ * An infeasible target gives out_score = -inf and -1 everywhere.  Ties go to the smaller source
+ * state (s before s - 1 before s - 2), and to S' - 2 over S' - 1 at the end.
+ * workspace (4-byte aligned) holds a 2-bit back-pointer per (t, s), 4 states per byte, rows padded
+ * to 32-bit words: vasr_ctc_align_workspace_bytes(B, L, Smax) = B * L * 4 * ceil((2 Smax + 1) / 16);
+ * workspace_bytes below that is VASR_EINVAL. */
+int vasr_ctc_align_f32(const float* emis, int B, int L, int Smax, const int32_t* targets,
+                       const int32_t* frames, const int32_t* tlen, void* workspace, int64_t workspace_bytes,
+                       int32_t* frame_state, int32_t* out_start, int32_t* out_end, float* out_score,
+                       void* stream);
+int64_t vasr_ctc_align_workspace_bytes(int B, int L, int Smax);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,374 @@
+// CTC loss (forward) and CTC forced alignment against a known transcript
+// (reference velocity_asr/training.py:47-104: F.log_softmax + nn.CTCLoss; the Viterbi form of
+// the same lattice is the forced alignment that belongs beside decode.py:74-125).
+//
+// Two stages.
+//   1. ctc_emissions_kernel: the only part that touches the (B, L, V) logits.  One wave per
+//      logit row reads the row once (16-byte loads where the row is 16-byte aligned, scalar
+//      loads otherwise -- the element -> lane assignment and the arithmetic are the same in
+//      both, so the result does not depend on the alignment), keeps a running (max, sum of
+//      exp) per lane, combines the 64 lanes, and gathers the blank's and the target tokens'
+//      log-probabilities into the compact emis (B, L, Smax + 1).  No (B, L, V) log-softmax
+//      tensor exists.  The row loop is branch-free and unrolled by 4, so a 1000-wide row's four
+//      loads per lane are in flight together (18.9 us against 21.0 us rolled at 32 x 501 x 1000).
+//   2. ctc_lattice_kernel: one workgroup per utterance walks the frames over the extended
+//      label sequence (S' = 2 tlen + 1 states, blanks interleaved).  Lane l keeps the R
+//      consecutive states l R .. l R + R - 1 in registers; R is even, so a lane's even slots
+//      are blanks and the only value it needs from outside is its left neighbour's last state,
+//      fetched with one DPP wave shift per frame.  One wave holds 64 R states; a longer
+//      target takes several waves, which hand that one boundary value over through LDS with one
+//      barrier per frame.  Emissions of the next eight frames (four at R = 8) are loaded while the
+//      current ones are consumed (the recursion is a serial chain per frame; an exposed load per frame
+//      would dominate it).  LOSS: log-sum-exp of the sources (fp32, maximum subtracted, -inf
+//      stays -inf) on the hardware exp2 / log2 (~1 ulp each; the rounding of alpha + emission at
+//      |alpha| in the hundreds to thousands is what sets the accuracy).  ALIGN:
+//      maximum of the sources with a 2-bit back-pointer per (t, s) in the caller's workspace, then
+//      a backtrack by thread 0.
+#include "vasr_internal.h"
+
+namespace vasr {
+namespace {
+
+constexpr int kMaxFrames = 8192;
+constexpr int kMaxTarget = 2048;
+constexpr int kEmisWaves = 4;   // logit rows per workgroup of ctc_emissions_kernel
+
+// ------------------------------------------------------------------ emissions
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+    return v;
+}
+
+// fold four more elements into a running (maximum m, sum s of exp(x - m))
+__device__ __forceinline__ void lse_fold(float& m, float& s, float x0, float x1, float x2, float x3) {
+    const float mn = fmaxf(fmaxf(m, fmaxf(x0, x1)), fmaxf(x2, x3));
+    const float ms = mn == -INFINITY ? 0.f : mn;  // all -inf so far: no inf - inf
+    s = s * fast_exp(m - ms) + ((fast_exp(x0 - ms) + fast_exp(x1 - ms)) + (fast_exp(x2 - ms) + fast_exp(x3 - ms)));
+    m = mn;
+}
+
+__global__ __launch_bounds__(kEmisWaves* kWave) void ctc_emissions_kernel(
+    const float* __restrict__ logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+    const int32_t* __restrict__ targets, int Smax, const int32_t* __restrict__ frames,
+    const int32_t* __restrict__ tlen, int blank, float* __restrict__ emis) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t r = (int64_t)blockIdx.x * kEmisWaves + (threadIdx.x >> 6);
+    if (r >= (int64_t)B * L) return;
+    const int b = (int)(r / L), t = (int)(r - (int64_t)b * L);
+    if (t >= min(max(frames[b], 0), L)) return;  // padding rows are never read
+    const float* row = logits + (int64_t)b * ld_utt + (int64_t)t * ld_row;
+    const bool wide = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+
+    // running maximum m and sum s of exp(x - m) over this lane's elements: group g = 64 c + lane
+    // of 4 consecutive elements, c = 0, 1, ...  The loops are branch-free (a lane past the last
+    // whole group loads that group again and folds in -inf, which changes nothing), so the
+    // unrolled loads of a row are all in flight together.
+    float m = -INFINITY, s = 0.f;
+    const int nfull = V >> 2, nch = (nfull + kWave - 1) / kWave;
+    if (wide) {
+        const float4* row4 = reinterpret_cast<const float4*>(row);
+#pragma unroll 4
+        for (int c = 0; c < nch; ++c) {
+            const int g = c * kWave + lane;
+            const float4 q = row4[min(g, nfull - 1)];
+            const bool in = g < nfull;
+            lse_fold(m, s, in ? q.x : -INFINITY, in ? q.y : -INFINITY, in ? q.z : -INFINITY, in ? q.w : -INFINITY);
+        }
+    } else {
+#pragma unroll 4
+        for (int c = 0; c < nch; ++c) {
+            const int g = c * kWave + lane;
+            const float* p = row + 4 * min(g, nfull - 1);
+            const float x0 = p[0], x1 = p[1], x2 = p[2], x3 = p[3];
+            const bool in = g < nfull;
+            lse_fold(m, s, in ? x0 : -INFINITY, in ? x1 : -INFINITY, in ? x2 : -INFINITY, in ? x3 : -INFINITY);
+        }
+    }
+    if ((V & 3) && lane == (nfull & (kWave - 1))) {  // the last, partial group: after that lane's whole ones
+        const float* p = row + 4 * nfull;
+        lse_fold(m, s, p[0], (V & 3) > 1 ? p[1] : -INFINITY, (V & 3) > 2 ? p[2] : -INFINITY, -INFINITY);
+    }
+    const float M = wave_max(m);
+    const float Ms = M == -INFINITY ? 0.f : M;
+    const float lse = logf(wave_sum(s * fast_exp(m - Ms)));  // of the row shifted by M
+
+    float* e = emis + r * (int64_t)(Smax + 1);
+    const int n = min(max(tlen[b], 0), Smax);
+    const int32_t* tg = targets + (int64_t)b * Smax;
+    for (int j = lane; j <= n; j += kWave) {
+        const int tok = j == 0 ? blank : tg[j - 1];
+        // a token id outside [0, V) is not read: its emission is -inf
+        e[j] = (tok >= 0 && tok < V) ? (row[tok] - Ms) - lse : -INFINITY;
+    }
+}
+
+// ------------------------------------------------------------------ lattice
+
+// v of lane - 1; lane 0 of the wave gets `first`.  (DPP wave_shr:1, bound_ctrl off: the lane
+// without a source keeps the old value.)
+__device__ __forceinline__ float from_left_lane(float v, float first) {
+    return __int_as_float(
+        __builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v), 0x138, 0xF, 0xF, false));
+}
+
+__device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
+
+// log(exp(a) + exp(b)) and log(exp(a) + exp(b) + exp(c)); -inf if every argument is
+__device__ __forceinline__ float lse2(float a, float b) {
+    const float m = fmaxf(a, b);
+    const float r = m + fast_log(1.0f + fast_exp(fminf(a, b) - m));
+    return m == -INFINITY ? m : r;
+}
+__device__ __forceinline__ float lse3(float a, float b, float c) {
+    const float m = fmaxf(a, fmaxf(b, c));
+    const float r = m + fast_log((fast_exp(a - m) + fast_exp(b - m)) + fast_exp(c - m));
+    return m == -INFINITY ? m : r;
+}
+
+// R states per lane (even), ALIGN: Viterbi with back-pointers instead of the sum.
+// blockDim.x = 64 * waves with 64 * waves * R >= 2 * Smax + 1.
+template <int R, bool ALIGN>
+__global__ __launch_bounds__(640) void ctc_lattice_kernel(
+    const float* __restrict__ emis, int L, int Smax, const int32_t* __restrict__ targets,
+    const int32_t* __restrict__ frames, const int32_t* __restrict__ tlen, float* __restrict__ out,
+    uint8_t* __restrict__ bp, int bp_row, int32_t* __restrict__ frame_state, int32_t* __restrict__ out_start,
+    int32_t* __restrict__ out_end) {
+    constexpr int H = R / 2;  // labels per lane
+    constexpr int kFrameGroup = R == 8 ? 4 : 8;  // frames whose emissions are in flight together (registers)
+    __shared__ float edge[2][16];
+    __shared__ float fin[2];
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const int nwaves = blockDim.x >> 6;
+    const int T = min(max(frames[b], 0), L);
+    const int n = min(max(tlen[b], 0), Smax);
+    const int S = 2 * n + 1;
+    const int E = Smax + 1;
+    const float* e = emis + (int64_t)b * L * E;
+    const int32_t* tg = targets + (int64_t)b * Smax;
+    const int s0 = tid * R;  // first state of this lane
+    const int j0 = tid * H;  // label of its first odd state
+
+    // label j may be entered from label j - 1 directly (no blank between) iff they differ
+    bool skip[H], live[H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const int j = j0 + h;
+        live[h] = j < n;
+        skip[h] = live[h] && j >= 1 && tg[j] != tg[j - 1];
+    }
+    if (tid == 0) fin[0] = fin[1] = -INFINITY;
+    if (ALIGN) {
+        for (int t = tid; t < L; t += blockDim.x) frame_state[(int64_t)b * L + t] = -1;
+        for (int j = tid; j < Smax; j += blockDim.x) out_start[(int64_t)b * Smax + j] = out_end[(int64_t)b * Smax + j] = -1;
+    }
+
+    // frame -1: all the mass in state 0, so frame 0 comes out of the same recursion
+    float a[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) a[k] = (s0 + k == 0) ? 0.f : -INFINITY;
+
+    // emissions of a group of frames: the blank's and this lane's labels'
+    float eb[2][kFrameGroup], el[2][kFrameGroup][H];
+    auto fetch = [&](int buf, int t0) {
+#pragma unroll
+        for (int g = 0; g < kFrameGroup; ++g) {
+            const int t = t0 + g;
+            const float* et = e + (int64_t)t * E;
+            eb[buf][g] = t < T ? et[0] : 0.f;
+#pragma unroll
+            for (int h = 0; h < H; ++h) el[buf][g][h] = (t < T && live[h]) ? et[1 + j0 + h] : -INFINITY;
+        }
+    };
+    auto step = [&](int t, float ebt, const float* elt) {
+        float first = -INFINITY;
+        if (nwaves > 1) {  // uniform per launch
+            if (lane == kWave - 1) edge[t & 1][wave] = a[R - 1];
+            __syncthreads();
+            if (wave > 0) first = edge[t & 1][wave - 1];
+        }
+        const float left = from_left_lane(a[R - 1], first);
+        float nw[R];
+        unsigned bits = 0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const float c0 = a[k];
+            const float c1 = k >= 1 ? a[k - 1] : left;
+            const float c2 = (k & 1) && skip[k >> 1] ? (k >= 2 ? a[k - 2] : left) : -INFINITY;
+            const float em = (k & 1) ? elt[k >> 1] : ebt;
+            if (ALIGN) {
+                // ties go to the smaller source state: s, then s - 1, then s - 2
+                float best = c0;
+                unsigned from = 0;
+                if (c1 > best) best = c1, from = 1;
+                if (c2 > best) best = c2, from = 2;
+                nw[k] = best + em;
+                bits |= from << (2 * k);
+            } else {
+                nw[k] = ((k & 1) ? lse3(c0, c1, c2) : lse2(c0, c1)) + em;  // a blank has two sources
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) a[k] = nw[k];
+        if (ALIGN) {  // 4 states per byte: byte s / 4 of row (b, t), bits 2 (s % 4)
+            uint8_t* rowp = bp + ((int64_t)b * L + t) * bp_row;
+            if (R == 4) {
+                if (tid < bp_row) rowp[tid] = (uint8_t)bits;
+            } else {
+                if (2 * tid < bp_row) reinterpret_cast<uint16_t*>(rowp)[tid] = (uint16_t)bits;
+            }
+        }
+    };
+
+    __syncthreads();  // fin
+    fetch(0, 0);
+    for (int t0 = 0; t0 < T; t0 += 2 * kFrameGroup) {  // two groups per trip: the buffers stay in registers
+        fetch(1, t0 + kFrameGroup);
+#pragma unroll
+        for (int g = 0; g < kFrameGroup; ++g)
+            if (t0 + g < T) step(t0 + g, eb[0][g], el[0][g]);
+        fetch(0, t0 + 2 * kFrameGroup);
+#pragma unroll
+        for (int g = 0; g < kFrameGroup; ++g)
+            if (t0 + kFrameGroup + g < T) step(t0 + kFrameGroup + g, eb[1][g], el[1][g]);
+    }
+
+    // the last two states
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        if (s0 + k == S - 1) fin[0] = a[k];
+        if (s0 + k == S - 2) fin[1] = a[k];
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const float hi = fin[0], lo = fin[1];  // states S - 1, S - 2
+    if (!ALIGN) {
+        const float m = fmaxf(hi, lo);
+        out[b] = m == -INFINITY ? INFINITY : -(m + logf(expf(hi - m) + expf(lo - m)));
+        return;
+    }
+    const float score = fmaxf(hi, lo);
+    out[b] = score;
+    if (score == -INFINITY) return;  // infeasible: everything stays -1
+    int s = lo >= hi ? S - 2 : S - 1;  // tie: the smaller state
+    int32_t* fs = frame_state + (int64_t)b * L;
+    int32_t* st = out_start + (int64_t)b * Smax;
+    int32_t* en = out_end + (int64_t)b * Smax;
+    int last = -1;
+    for (int t = T - 1; t >= 0; --t) {
+        if (s & 1) {
+            const int j = s >> 1;
+            fs[t] = j;
+            if (j != last) en[j] = t + 1, last = j;
+            st[j] = t;
+        }
+        const uint8_t w = bp[((int64_t)b * L + t) * bp_row + (s >> 2)];
+        s -= (w >> (2 * (s & 3))) & 3;
+    }
+}
+
+int check_lattice(const char* who, const float* emis, int B, int L, int Smax, const int32_t* targets,
+                  const int32_t* frames, const int32_t* tlen) {
+    VASR_CHECK_ARG(emis && frames && tlen && (targets || Smax == 0), "%s: null pointer", who);
+    VASR_CHECK_ARG(B >= 0 && L >= 1 && L <= kMaxFrames && Smax >= 0, "%s: bad shape B=%d L=%d (1..%d) Smax=%d", who,
+                   B, L, kMaxFrames, Smax);
+    if (Smax > kMaxTarget) {
+        set_error("%s: Smax=%d above the supported %d", who, Smax, kMaxTarget);
+        return VASR_EUNSUPPORTED;
+    }
+    return VASR_OK;
+}
+
+// 4 back-pointers per byte, rows padded to whole 32-bit words
+inline int bp_row_bytes(int Smax) { return 4 * ((2 * Smax + 1 + 15) / 16); }
+
+}  // namespace
+}  // namespace vasr
+
+VASR_API int vasr_ctc_emissions_f32(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                                    const int32_t* targets, int Smax, const int32_t* frames, const int32_t* tlen,
+                                    int blank, float* emis, void* stream) {
+    using namespace vasr;
+    VASR_CHECK_ARG(logits && frames && tlen && emis && (targets || Smax == 0), "vasr_ctc_emissions_f32: null pointer");
+    VASR_CHECK_ARG(B >= 0 && L >= 1 && L <= kMaxFrames && V >= 1 && Smax >= 0 && ld_row >= V,
+                   "vasr_ctc_emissions_f32: bad shape B=%d L=%d (1..%d) V=%d Smax=%d ld_row=%lld", B, L, kMaxFrames, V,
+                   Smax, (long long)ld_row);
+    VASR_CHECK_ARG(blank >= 0 && blank < V, "vasr_ctc_emissions_f32: blank=%d outside [0, %d)", blank, V);
+    if (Smax > kMaxTarget) {
+        set_error("vasr_ctc_emissions_f32: Smax=%d above the supported %d", Smax, kMaxTarget);
+        return VASR_EUNSUPPORTED;
+    }
+    if (B == 0) return VASR_OK;
+    const int64_t rows = (int64_t)B * L;
+    hipLaunchKernelGGL(ctc_emissions_kernel, dim3((unsigned)((rows + kEmisWaves - 1) / kEmisWaves)),
+                       dim3(kEmisWaves * kWave), 0, as_stream(stream), logits, ld_row, ld_utt, B, L, V, targets, Smax,
+                       frames, tlen, blank, emis);
+    return launch_status("vasr_ctc_emissions_f32");
+}
+
+namespace vasr {
+namespace {
+
+template <bool ALIGN>
+void launch_lattice(const float* emis, int B, int L, int Smax, const int32_t* targets, const int32_t* frames,
+                    const int32_t* tlen, float* out, uint8_t* bp, int32_t* frame_state, int32_t* out_start,
+                    int32_t* out_end, hipStream_t s) {
+    const int S = 2 * Smax + 1;
+    const int row = bp_row_bytes(Smax);
+#define VASR_LATTICE(R, THREADS)                                                                                   \
+    hipLaunchKernelGGL((ctc_lattice_kernel<R, ALIGN>), dim3(B), dim3(THREADS), 0, s, emis, L, Smax, targets, frames, \
+                       tlen, out, bp, row, frame_state, out_start, out_end)
+    // the fewest waves that hold the lattice; within one wave, the fewest states per lane
+    if constexpr (!ALIGN) {  // (a lane's back-pointers fill whole bytes from R = 4 on)
+        if (S <= 2 * kWave) {
+            VASR_LATTICE(2, kWave);
+            return;
+        }
+    }
+    if (S <= 4 * kWave) {
+        VASR_LATTICE(4, kWave);
+    } else {
+        VASR_LATTICE(8, kWave * ((S + 8 * kWave - 1) / (8 * kWave)));  // <= 9 waves at Smax = 2048
+    }
+#undef VASR_LATTICE
+}
+
+}  // namespace
+}  // namespace vasr
+
+VASR_API int vasr_ctc_loss_f32(const float* emis, int B, int L, int Smax, const int32_t* targets,
+                               const int32_t* frames, const int32_t* tlen, float* out_nll, void* stream) {
+    using namespace vasr;
+    const int rc = check_lattice("vasr_ctc_loss_f32", emis, B, L, Smax, targets, frames, tlen);
+    if (rc != VASR_OK) return rc;
+    VASR_CHECK_ARG(out_nll, "vasr_ctc_loss_f32: null pointer");
+    if (B == 0) return VASR_OK;
+    launch_lattice<false>(emis, B, L, Smax, targets, frames, tlen, out_nll, nullptr, nullptr, nullptr, nullptr,
+                          as_stream(stream));
+    return launch_status("vasr_ctc_loss_f32");
+}
+
+VASR_API int64_t vasr_ctc_align_workspace_bytes(int B, int L, int Smax) {
+    if (B < 0 || L < 0 || Smax < 0) return 0;
+    return (int64_t)B * L * vasr::bp_row_bytes(Smax);
+}
+
+VASR_API int vasr_ctc_align_f32(const float* emis, int B, int L, int Smax, const int32_t* targets,
+                                const int32_t* frames, const int32_t* tlen, void* workspace, int64_t workspace_bytes,
+                                int32_t* frame_state, int32_t* out_start, int32_t* out_end, float* out_score,
+                                void* stream) {
+    using namespace vasr;
+    const int rc = check_lattice("vasr_ctc_align_f32", emis, B, L, Smax, targets, frames, tlen);
+    if (rc != VASR_OK) return rc;
+    VASR_CHECK_ARG(workspace && frame_state && out_score && ((out_start && out_end) || Smax == 0),
+                   "vasr_ctc_align_f32: null pointer");
+    VASR_CHECK_ARG(workspace_bytes >= vasr_ctc_align_workspace_bytes(B, L, Smax),
+                   "vasr_ctc_align_f32: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                   (long long)vasr_ctc_align_workspace_bytes(B, L, Smax));
+    if (B == 0) return VASR_OK;
+    launch_lattice<true>(emis, B, L, Smax, targets, frames, tlen, out_score, static_cast<uint8_t*>(workspace),
+                         frame_state, out_start, out_end, as_stream(stream));
+    return launch_status("vasr_ctc_align_f32");
+}

@@ -3,6 +3,7 @@
 Greedy decoding runs on the device: an argmax kernel over the vocabulary and a
 per-utterance collapse kernel (blank removal, repeat collapse, optional run
 timestamps), so only the kept token ids cross PCIe instead of (B, L, V) logits.
+ctc_forced_align scores and aligns a known transcript on the device (not in the reference).
 Token -> text conversion is host string handling, as in the reference.
 """
 
@@ -118,6 +119,39 @@ def _ctc_beam_search_host(logits: torch.Tensor, beam_width: int, blank_token: in
     return all_results
 
 
+def ctc_forced_align(logits: torch.Tensor, targets, input_lengths=None, target_lengths=None,
+                     blank_token: int = BLANK_TOKEN) -> List[Tuple[float, List[Tuple[int, int]], List[int]]]:
+    """CTC forced alignment of a KNOWN transcript: the most probable path through the CTC lattice
+    of `targets` (vasr_ctc_emissions_f32 + vasr_ctc_align_f32), where
+    ctc_greedy_decode_with_timestamps only timestamps the model's own guess.
+
+    logits (B, L, V); targets (B, Smax) token ids (a tensor, or a list of token lists, which also
+    gives target_lengths); input_lengths / target_lengths (B,), default L / Smax.  Returns per
+    utterance (score, [(start_frame, end_frame), ...] per target token, frame_labels): the path's
+    log-probability; each token's first frame and one past its last, the convention of
+    ctc_greedy_decode_with_timestamps; and for each of the L frames the target INDEX it emits,
+    -1 for blank and past input_lengths.
+    A transcript that does not fit its frames has score -inf and (-1, -1) spans.
+    """
+    logits = _on_device(logits)
+    if logits.dim() != 3:
+        raise ValueError("ctc_forced_align: logits must be (B, L, V)")
+    B, Lq, _ = logits.shape
+    if not isinstance(targets, torch.Tensor):
+        rows = [list(r) for r in targets]
+        if target_lengths is None:
+            target_lengths = [len(r) for r in rows]
+        width = max((len(r) for r in rows), default=0)
+        targets = torch.tensor([r + [blank_token] * (width - len(r)) for r in rows], dtype=torch.int32).reshape(
+            len(rows), width)
+    emis, tg, frames, tlen = ops.ctc_emissions(logits, targets, input_lengths, target_lengths, blank_token)
+    state, st, en, score = ops.ctc_align(emis, tg, frames, tlen)
+    state, st, en, score = state.cpu().numpy(), st.cpu().numpy(), en.cpu().numpy(), score.cpu().numpy()
+    tlen = tlen.cpu().numpy().clip(0, tg.shape[1])
+    return [(float(score[b]), [(int(s), int(e)) for s, e in zip(st[b, :tlen[b]], en[b, :tlen[b]])],
+             state[b].tolist()) for b in range(B)]
+
+
 class CTCDecoder:
     """CTC decoder with vocabulary (reference decode.py:220-327)."""
 
@@ -139,6 +173,11 @@ class CTCDecoder:
                     result.text = self._tokens_to_text(result.tokens)
             return beam_results
         return [self._tokens_to_text(results[0].tokens) if results else "" for results in beam_results]
+
+    def align(self, logits: torch.Tensor, texts: List[str], input_lengths=None):
+        """Forced alignment of one transcript per utterance (text_to_tokens, then ctc_forced_align)."""
+        return ctc_forced_align(logits, [self.text_to_tokens(t) for t in texts], input_lengths=input_lengths,
+                                blank_token=self.blank_token)
 
     def _tokens_to_text(self, tokens: List[int]) -> str:
         chars = [self.vocabulary[t] if 0 <= t < self.vocab_size else "<unk>" for t in tokens]

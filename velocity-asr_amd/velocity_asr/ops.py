@@ -923,3 +923,89 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0):
                                        toks.data_ptr(), lens.data_ptr(), scores.data_ptr(), nbeams.data_ptr(),
                                        stream_of(x)), "vasr_ctc_beam_search")
     return toks, lens, scores, nbeams
+
+
+def _ctc_lengths(name: str, t, B: int, device, default: int) -> torch.Tensor:
+    """Per-utterance lengths as a contiguous int32 (B,) device tensor.  A device tensor is used
+    (cast if needed) without any host synchronisation; a host tensor, a sequence or None (all
+    `default`) is copied up."""
+    if t is None:
+        return torch.full((B,), int(default), device=device, dtype=torch.int32)
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype == torch.bool or tuple(t.shape) != (B,):
+        raise ValueError(f"{name}: expected {B} integer lengths, got {t.dtype} {tuple(t.shape)}")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _ctc_targets(who: str, targets: torch.Tensor, B: int, device) -> torch.Tensor:
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError(f"{who}: targets must be a (B, Smax) tensor")
+    if targets.dtype.is_floating_point or targets.dtype == torch.bool:
+        raise TypeError(f"{who}: targets must be integer token ids, got {targets.dtype}")
+    return targets.to(device=device, dtype=torch.int32).contiguous()
+
+
+def ctc_emissions(logits: torch.Tensor, targets: torch.Tensor, frames=None, tlen=None, blank: int = 0):
+    """(B, L, V) logits + (B, Smax) targets -> (emis (B, L, Smax + 1), targets, frames, tlen): the
+    log-softmax values of the blank and of each target token per frame, and the int32 device
+    forms of the other arguments as ctc_loss / ctc_align take them.  One pass over the logits; no
+    (B, L, V) log-softmax tensor.  Entries of frames >= frames[b] and slots > tlen[b] are
+    unspecified.  frames / tlen: device or host lengths, None = L / Smax."""
+    _cuda_f32("ctc_emissions.logits", logits)
+    if logits.dim() != 3:
+        raise ValueError("ctc_emissions: logits must be (B, L, V)")
+    x = logits if logits.stride(-1) == 1 else logits.contiguous()
+    B, Lq, V = x.shape
+    dev = x.device
+    tg = _ctc_targets("ctc_emissions", targets, B, dev)
+    Smax = tg.shape[1]
+    fr = _ctc_lengths("ctc_emissions.frames", frames, B, dev, Lq)
+    tl = _ctc_lengths("ctc_emissions.tlen", tlen, B, dev, Smax)
+    emis = torch.empty((B, Lq, Smax + 1), device=dev, dtype=torch.float32)
+    check(L.lib().vasr_ctc_emissions_f32(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, tg.data_ptr(), Smax,
+                                         fr.data_ptr(), tl.data_ptr(), int(blank), emis.data_ptr(), stream_of(x)),
+          "vasr_ctc_emissions_f32")
+    return emis, tg, fr, tl
+
+
+def _ctc_lattice_args(who: str, emis: torch.Tensor, targets: torch.Tensor, frames: torch.Tensor, tlen: torch.Tensor):
+    _cuda_f32(f"{who}.emis", emis)
+    if emis.dim() != 3 or not emis.is_contiguous():
+        raise ValueError(f"{who}: emis must be a contiguous (B, L, Smax + 1) tensor")
+    B, Lq, E = emis.shape
+    dev = emis.device
+    tg = _ctc_targets(who, targets, B, dev)
+    if tg.shape[1] != E - 1:
+        raise ValueError(f"{who}: targets of width {tg.shape[1]} for emissions of {E - 1} slots")
+    fr = _ctc_lengths(f"{who}.frames", frames, B, dev, Lq)
+    return B, Lq, E - 1, tg, fr, _ctc_lengths(f"{who}.tlen", tlen, B, dev, E - 1)
+
+
+def ctc_loss(emis: torch.Tensor, targets: torch.Tensor, frames=None, tlen=None) -> torch.Tensor:
+    """Negative log-likelihood (B,) float32 of each utterance's targets over ctc_emissions' output;
+    +inf for an infeasible target.  Enqueued on the current stream, no host synchronisation."""
+    B, Lq, Smax, tg, fr, tl = _ctc_lattice_args("ctc_loss", emis, targets, frames, tlen)
+    nll = torch.empty((B,), device=emis.device, dtype=torch.float32)
+    check(L.lib().vasr_ctc_loss_f32(emis.data_ptr(), B, Lq, Smax, tg.data_ptr(), fr.data_ptr(), tl.data_ptr(),
+                                    nll.data_ptr(), stream_of(emis)), "vasr_ctc_loss_f32")
+    return nll
+
+
+def ctc_align(emis: torch.Tensor, targets: torch.Tensor, frames=None, tlen=None):
+    """Best (Viterbi) CTC path of each utterance's targets over ctc_emissions' output ->
+    (frame_state (B, L) int32: target index per frame, -1 = blank / padding; start, end (B, Smax)
+    int32: token j's first frame and one past its last; score (B,) float32), all on the device.
+    An infeasible target has score -inf and -1 everywhere."""
+    B, Lq, Smax, tg, fr, tl = _ctc_lattice_args("ctc_align", emis, targets, frames, tlen)
+    dev = emis.device
+    nbytes = int(L.lib().vasr_ctc_align_workspace_bytes(B, Lq, Smax))
+    ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.int32)
+    state = torch.empty((B, Lq), device=dev, dtype=torch.int32)
+    st = torch.empty((B, Smax), device=dev, dtype=torch.int32)
+    en = torch.empty((B, Smax), device=dev, dtype=torch.int32)
+    score = torch.empty((B,), device=dev, dtype=torch.float32)
+    check(L.lib().vasr_ctc_align_f32(emis.data_ptr(), B, Lq, Smax, tg.data_ptr(), fr.data_ptr(), tl.data_ptr(),
+                                     ws.data_ptr(), nbytes, state.data_ptr(), st.data_ptr(), en.data_ptr(),
+                                     score.data_ptr(), stream_of(emis)), "vasr_ctc_align_f32")
+    return state, st, en, score

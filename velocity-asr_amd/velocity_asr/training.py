@@ -1,12 +1,83 @@
-"""Evaluation metrics used by scripts/evaluate.py (reference velocity_asr/training.py:412-501).
+"""Evaluation-side pieces of reference velocity_asr/training.py: the CTC loss that
+Trainer.eval_step scores a checkpoint with (training.py:47-104, :273-299) and the WER/CER
+metrics scripts/evaluate.py imports (training.py:412-501).
 
-Training itself (CTCLoss, schedulers, Trainer) is outside this inference build's scope
-(SURVEY §2 row 8); only the WER/CER helpers that evaluate.py imports are provided.
+CTCLoss here is the FORWARD loss on the HIP path (vasr_ctc_emissions_f32 + vasr_ctc_loss_f32):
+it scores a known transcript and has no backward pass.  Training itself (gradients, schedulers,
+Trainer) stays outside this inference build's scope.
 """
 
 from __future__ import annotations
 
 from typing import List, Sequence
+
+import torch
+import torch.nn as nn
+
+from . import ops
+
+
+class CTCLoss(nn.Module):
+    """Forward CTC loss with the reference's signature and values (training.py:47-104).
+
+    The reference takes F.log_softmax of the (B, L, V) logits and calls nn.CTCLoss; here one pass
+    over the logits keeps only the blank's and the target tokens' log-probabilities, and a lattice
+    kernel sums the paths, so no (B, L, V) log-softmax tensor is ever allocated.  The result is a
+    device tensor.  Forward only: logits that require grad (outside torch.no_grad()) are refused.
+
+    Args:
+        blank_token: index of the blank token
+        reduction: 'mean' (mean over the batch of nll_b / max(target_length_b, 1)), 'sum', 'none'
+        zero_infinity: replace the +inf loss of an infeasible target by 0
+    """
+
+    def __init__(self, blank_token: int = 0, reduction: str = "mean", zero_infinity: bool = True):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"CTCLoss: {reduction} is not a valid value for reduction")
+        self.blank_token = blank_token
+        self.reduction = reduction
+        self.zero_infinity = zero_infinity
+
+    def forward(self, logits: torch.Tensor, targets: torch.Tensor, input_lengths: torch.Tensor,
+                target_lengths: torch.Tensor) -> torch.Tensor:
+        """logits (B, L, V); targets (B, Smax), each row read up to its target length, or 1-D, all
+        utterances' targets concatenated (entries equal to the blank are dropped first, as
+        training.py:95-99); input_lengths, target_lengths (B,) on the device or the host."""
+        from .decode import _on_device
+
+        if logits.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(
+                "velocity_asr.training.CTCLoss is forward-only (evaluation): it has no backward pass. "
+                "Call it under torch.no_grad() or on detached logits.")
+        if logits.dim() != 3:
+            raise ValueError("CTCLoss: logits must be (batch, seq_len, vocab_size)")
+        logits = _on_device(logits.detach())
+        B = logits.shape[0]
+        if targets.dim() == 1:
+            targets = self._pad_concatenated(targets, target_lengths, B)
+        emis, tg, frames, tlen = ops.ctc_emissions(logits, targets, input_lengths, target_lengths, self.blank_token)
+        nll = ops.ctc_loss(emis, tg, frames, tlen)
+        if self.zero_infinity:
+            nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
+        if self.reduction == "none":
+            return nll
+        if self.reduction == "sum":
+            return nll.sum()
+        return (nll / tlen.clamp(min=1).to(nll.dtype)).mean()
+
+    def _pad_concatenated(self, targets: torch.Tensor, target_lengths, B: int) -> torch.Tensor:
+        """1-D concatenated targets -> (B, Smax) rows (host bookkeeping: this form reads the lengths)."""
+        flat = targets[targets != self.blank_token].cpu()
+        lens = [int(n) for n in torch.as_tensor(target_lengths).cpu().tolist()]
+        if len(lens) != B or sum(lens) > flat.numel():
+            raise ValueError(f"CTCLoss: target_lengths {lens} do not fit {flat.numel()} concatenated targets")
+        out = torch.zeros((B, max(lens, default=0)), dtype=torch.int32)
+        pos = 0
+        for b, n in enumerate(lens):
+            out[b, :n] = flat[pos:pos + n]
+            pos += n
+        return out
 
 
 def _edit_distance(a: Sequence, b: Sequence) -> int:
