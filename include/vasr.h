@@ -447,7 +447,8 @@ int vasr_ctc_collapse_keys(const uint64_t* keys, int64_t ld, int slots, int B, i
  * Forward-only scoring of a KNOWN transcript (training.py:47-104: F.log_softmax + nn.CTCLoss as
  * Trainer.eval_step, training.py:273-299, uses them for eval_loss), and the Viterbi form of the
  * same lattice: per-token frame spans, the companion of ctc_greedy_decode_with_timestamps
- * (decode.py:74-125), which only timestamps the model's own guess.  No gradients.
+ * (decode.py:74-125), which only timestamps the model's own guess.  The gradient of the loss is
+ * the next section.
  *
  * Common arguments: targets (B, Smax) int32 (may be NULL if Smax == 0); frames[B] and tlen[B]
  * device int32, clamped to [0, L] and [0, Smax]; rows t >= frames[b] and target slots
@@ -490,6 +491,58 @@ int vasr_ctc_align_f32(const float* emis, int B, int L, int Smax, const int32_t*
                        int32_t* frame_state, int32_t* out_start, int32_t* out_end, float* out_score,
                        void* stream);
 int64_t vasr_ctc_align_workspace_bytes(int B, int L, int Smax);
+
+/* ------------------------------------------------------------------ CTC loss, backward
+ * The gradient of vasr_ctc_loss_f32's nll with respect to the logits, in three launches, with the
+ * common arguments and limits above.  These three symbols were ADDED to ABI 20 without a bump:
+ * they are purely additive (no existing symbol, argument or result changed), so every caller of
+ * ABI 20 keeps working unchanged, and a caller that needs them finds out by looking the symbols up.
+ *
+ * For utterance b with T = frames[b], n = tlen[b], S' = 2 n + 1 and e[t][s] the emission of state s
+ * (emis[b][t][0] for a blank, emis[b][t][1 + j] for label j), all in fp32 log space:
+ *   alpha as vasr_ctc_loss_f32;
+ *   beta[T-1][s] = e[T-1][s] for s in {S'-1, S'-2}, -inf otherwise;
+ *   beta[t][s]   = e[t][s] + lse(beta[t+1][s], beta[t+1][s+1], beta[t+1][s+2]), the last term only
+ *                  for a label s whose successor label differs (both include the emission at t, the
+ *                  convention of torch.nn.functional.ctc_loss);
+ *   gamma[t][s]  = exp(alpha[t][s] + beta[t][s] - e[t][s] + nll).
+ *
+ * Stage 2a': vasr_ctc_loss_f32 that also keeps alpha (B, L, 2 Smax + 1): alpha[b][t][s] for t < T,
+ * s < S'; the other entries are left unwritten.  out_nll is bitwise vasr_ctc_loss_f32's.
+ * alpha_elems (floats available at alpha) below B * L * (2 Smax + 1) is VASR_EINVAL. */
+int vasr_ctc_loss_alpha_f32(const float* emis, int B, int L, int Smax, const int32_t* targets,
+                            const int32_t* frames, const int32_t* tlen, float* out_nll, float* alpha,
+                            int64_t alpha_elems, void* stream);
+
+/* Stage 3: the posterior occupancy occ (B, L, Smax + 1), linear space, from emis, the alpha and the
+ * nll of vasr_ctc_loss_alpha_f32:
+ *   occ[b][t][0]     = sum of gamma[t][s] over the blank states (even s),
+ *   occ[b][t][1 + j] = gamma[t][2 j + 1]                                   (t < T, j < n),
+ * and exact zeros in every other entry: rows t >= T, slots past n, and all of an utterance whose
+ * nll is +inf.  Every entry of occ is written, and lies in [0, 1]: a value that fp32 rounding
+ * (alpha + beta at magnitudes in the thousands) puts above 1 is clamped to it, which only moves it
+ * towards the exact posterior.  One workgroup per utterance; the blank sum is
+ * reduced in a fixed order (within a wave, then over the waves in wave order), so each value
+ * depends on its own utterance only and repeats bitwise. */
+int vasr_ctc_occupancy_f32(const float* emis, const float* alpha, int64_t alpha_elems, const float* nll, int B,
+                           int L, int Smax, const int32_t* targets, const int32_t* frames, const int32_t* tlen,
+                           float* occ, void* stream);
+
+/* Stage 4: the gradient, grad (B, L, V) contiguous fp32, from the logits (strides as
+ * vasr_ctc_emissions_f32; any V, any alignment) and occ:
+ *   grad[b][t][v] = scale[b] * (softmax(logits[b][t])[v] - sum of occ[b][t][slot] over the slots
+ *                   whose token is v)            (t < T; slot 0 is `blank`, slot 1 + j targets[b][j]),
+ *   grad[b][t][:] = 0                            (t >= T; those logit rows are not read).
+ * scale[B] (device fp32) is the upstream gradient of nll_b.  The row's log-sum-exp is recomputed as
+ * in stage 1, so no (B, L, V) log-softmax and no (B, L) side buffer exists.  Slots that share a
+ * token are summed in ascending slot order and every column has one writer of its final value (no
+ * floating-point atomics): the result repeats bitwise.  A token id outside [0, V) is never used as
+ * an index.  workspace: B * (Smax + 1) int32 (the per-utterance chain of slots with the same token,
+ * built by a first small launch); workspace_elems below that is VASR_EINVAL. */
+int vasr_ctc_grad_logits_f32(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                             const int32_t* targets, int Smax, const int32_t* frames, const int32_t* tlen,
+                             int blank, const float* occ, const float* scale, int32_t* workspace,
+                             int64_t workspace_elems, float* grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,10 @@ _SIGNATURES = {
     "vasr_ctc_loss_f32": ([c_p] + [ctypes.c_int] * 3 + [c_p] * 5, ctypes.c_int),
     "vasr_ctc_align_f32": ([c_p] + [ctypes.c_int] * 3 + [c_p] * 4 + [c_i64] + [c_p] * 5, ctypes.c_int),
     "vasr_ctc_align_workspace_bytes": ([ctypes.c_int] * 3, c_i64),
+    "vasr_ctc_loss_alpha_f32": ([c_p] + [ctypes.c_int] * 3 + [c_p] * 5 + [c_i64, c_p], ctypes.c_int),
+    "vasr_ctc_occupancy_f32": ([c_p, c_p, c_i64, c_p] + [ctypes.c_int] * 3 + [c_p] * 5, ctypes.c_int),
+    "vasr_ctc_grad_logits_f32": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 3 + [c_p, ctypes.c_int, c_p, c_p, ctypes.c_int,
+                                                                            c_p, c_p, c_p, c_i64, c_p, c_p], ctypes.c_int),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -1009,3 +1009,60 @@ def ctc_align(emis: torch.Tensor, targets: torch.Tensor, frames=None, tlen=None)
                                      ws.data_ptr(), nbytes, state.data_ptr(), st.data_ptr(), en.data_ptr(),
                                      score.data_ptr(), stream_of(emis)), "vasr_ctc_align_f32")
     return state, st, en, score
+
+
+def ctc_loss_alpha(emis: torch.Tensor, targets: torch.Tensor, frames=None, tlen=None):
+    """ctc_loss that also keeps the forward lattice -> (nll (B,), alpha (B, L, 2 Smax + 1) float32):
+    nll is bitwise ctc_loss's; alpha[b][t][s] is written for t < frames[b], s <= 2 tlen[b] and
+    unspecified elsewhere.  The forward half of the differentiable loss."""
+    B, Lq, Smax, tg, fr, tl = _ctc_lattice_args("ctc_loss_alpha", emis, targets, frames, tlen)
+    nll = torch.empty((B,), device=emis.device, dtype=torch.float32)
+    alpha = torch.empty((B, Lq, 2 * Smax + 1), device=emis.device, dtype=torch.float32)
+    check(L.lib().vasr_ctc_loss_alpha_f32(emis.data_ptr(), B, Lq, Smax, tg.data_ptr(), fr.data_ptr(), tl.data_ptr(),
+                                          nll.data_ptr(), alpha.data_ptr(), alpha.numel(), stream_of(emis)),
+          "vasr_ctc_loss_alpha_f32")
+    return nll, alpha
+
+
+def ctc_occupancy(emis: torch.Tensor, alpha: torch.Tensor, nll: torch.Tensor, targets: torch.Tensor, frames=None,
+                  tlen=None) -> torch.Tensor:
+    """Posterior occupancy (B, L, Smax + 1) float32 of the transcript per frame, from ctc_emissions'
+    and ctc_loss_alpha's outputs: [..., 0] the blank (all blank states), [..., 1 + j] target j, in
+    linear space.  Padding rows and slots, and an infeasible utterance (nll = +inf), are exact zeros."""
+    B, Lq, Smax, tg, fr, tl = _ctc_lattice_args("ctc_occupancy", emis, targets, frames, tlen)
+    _cuda_f32("ctc_occupancy.alpha", alpha)
+    _cuda_f32("ctc_occupancy.nll", nll)
+    if tuple(alpha.shape) != (B, Lq, 2 * Smax + 1) or not alpha.is_contiguous():
+        raise ValueError(f"ctc_occupancy: alpha must be a contiguous ({B}, {Lq}, {2 * Smax + 1}) tensor")
+    if tuple(nll.shape) != (B,) or not nll.is_contiguous():
+        raise ValueError(f"ctc_occupancy: nll must be a contiguous ({B},) tensor")
+    occ = torch.empty((B, Lq, Smax + 1), device=emis.device, dtype=torch.float32)
+    check(L.lib().vasr_ctc_occupancy_f32(emis.data_ptr(), alpha.data_ptr(), alpha.numel(), nll.data_ptr(), B, Lq, Smax,
+                                         tg.data_ptr(), fr.data_ptr(), tl.data_ptr(), occ.data_ptr(), stream_of(emis)),
+          "vasr_ctc_occupancy_f32")
+    return occ
+
+
+def ctc_grad_logits(logits: torch.Tensor, occ: torch.Tensor, targets: torch.Tensor, frames, tlen,
+                    scale: torch.Tensor, blank: int = 0) -> torch.Tensor:
+    """d(sum_b scale[b] nll_b) / d logits -> contiguous (B, L, V) float32:
+    scale[b] (softmax(logits[b, t]) - occupancy gathered per token) for t < frames[b], zeros after.
+    One pass that recomputes each row's log-sum-exp; no (B, L, V) log-softmax tensor, no atomics."""
+    _cuda_f32("ctc_grad_logits.logits", logits)
+    if logits.dim() != 3:
+        raise ValueError("ctc_grad_logits: logits must be (B, L, V)")
+    x = logits if logits.stride(-1) == 1 else logits.contiguous()
+    V = x.shape[2]
+    B, Lq, Smax, tg, fr, tl = _ctc_lattice_args("ctc_grad_logits", occ, targets, frames, tlen)
+    if tuple(x.shape[:2]) != (B, Lq):
+        raise ValueError(f"ctc_grad_logits: logits {tuple(x.shape)} for an occupancy of {B} x {Lq} rows")
+    _cuda_f32("ctc_grad_logits.scale", scale)
+    if tuple(scale.shape) != (B,) or not scale.is_contiguous():
+        raise ValueError(f"ctc_grad_logits: scale must be a contiguous ({B},) tensor")
+    chain = torch.empty((B, Smax + 1), device=x.device, dtype=torch.int32)
+    grad = torch.empty((B, Lq, V), device=x.device, dtype=torch.float32)
+    check(L.lib().vasr_ctc_grad_logits_f32(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, tg.data_ptr(), Smax,
+                                           fr.data_ptr(), tl.data_ptr(), int(blank), occ.data_ptr(), scale.data_ptr(),
+                                           chain.data_ptr(), chain.numel(), grad.data_ptr(), stream_of(x)),
+          "vasr_ctc_grad_logits_f32")
+    return grad

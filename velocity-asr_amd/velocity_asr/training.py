@@ -2,9 +2,12 @@
 Trainer.eval_step scores a checkpoint with (training.py:47-104, :273-299) and the WER/CER
 metrics scripts/evaluate.py imports (training.py:412-501).
 
-CTCLoss here is the FORWARD loss on the HIP path (vasr_ctc_emissions_f32 + vasr_ctc_loss_f32):
-it scores a known transcript and has no backward pass.  Training itself (gradients, schedulers,
-Trainer) stays outside this inference build's scope.
+CTCLoss here is the loss on the HIP path (vasr_ctc_emissions_f32 + vasr_ctc_loss_f32): by default
+forward only, scoring a known transcript; with differentiable=True it also has a backward pass
+(vasr_ctc_loss_alpha_f32 in the forward, vasr_ctc_occupancy_f32 + vasr_ctc_grad_logits_f32 in the
+backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.CTCLoss.  The
+rest of training (backward passes of the model's kernels, schedulers, Trainer) stays outside this
+inference build's scope.
 """
 
 from __future__ import annotations
@@ -17,27 +20,61 @@ import torch.nn as nn
 from . import ops
 
 
+class _CTCNll(torch.autograd.Function):
+    """Per-utterance nll (B,) of float32 device logits, with the gradient to them; targets and
+    lengths in ops.ctc_emissions' device forms.  Forward: emissions + the lattice that keeps alpha.
+    Backward: occupancy (beta walked over the same lattice) + one pass over the logits that writes
+    scale[b] (softmax - occupancy); scale[b] is the upstream gradient of nll_b, replaced for an
+    infeasible utterance (nll = +inf) by 0 under zero_infinity and by NaN otherwise, as the
+    reference yields.  Everything is enqueued on the current stream: no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, logits, tg, frames, tlen, blank, zero_infinity):
+        x = logits.detach()
+        emis, tg, frames, tlen = ops.ctc_emissions(x, tg, frames, tlen, blank)
+        nll, alpha = ops.ctc_loss_alpha(emis, tg, frames, tlen)
+        ctx.save_for_backward(x, emis, alpha, nll, tg, frames, tlen)
+        ctx.blank, ctx.zero_infinity = blank, zero_infinity
+        return nll
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_nll):
+        x, emis, alpha, nll, tg, frames, tlen = ctx.saved_tensors
+        scale = grad_nll.to(dtype=torch.float32)
+        infeasible = torch.full_like(scale, 0.0 if ctx.zero_infinity else float("nan"))
+        scale = torch.where(torch.isinf(nll), infeasible, scale)
+        occ = ops.ctc_occupancy(emis, alpha, nll, tg, frames, tlen)
+        grad = ops.ctc_grad_logits(x, occ, tg, frames, tlen, scale.contiguous(), ctx.blank)
+        return grad, None, None, None, None, None
+
+
 class CTCLoss(nn.Module):
-    """Forward CTC loss with the reference's signature and values (training.py:47-104).
+    """CTC loss with the reference's signature and values (training.py:47-104).
 
     The reference takes F.log_softmax of the (B, L, V) logits and calls nn.CTCLoss; here one pass
     over the logits keeps only the blank's and the target tokens' log-probabilities, and a lattice
     kernel sums the paths, so no (B, L, V) log-softmax tensor is ever allocated.  The result is a
-    device tensor.  Forward only: logits that require grad (outside torch.no_grad()) are refused.
+    device tensor.  By default forward only: logits that require grad (outside torch.no_grad()) are
+    refused.  With differentiable=True such logits get their gradient from the device backward
+    pass (_CTCNll), in their own dtype and shape; the loss value is bitwise the forward-only one.
 
     Args:
         blank_token: index of the blank token
         reduction: 'mean' (mean over the batch of nll_b / max(target_length_b, 1)), 'sum', 'none'
-        zero_infinity: replace the +inf loss of an infeasible target by 0
+        zero_infinity: replace the +inf loss of an infeasible target by 0 (and its gradient by 0)
+        differentiable: give logits that require grad a backward pass instead of refusing them
     """
 
-    def __init__(self, blank_token: int = 0, reduction: str = "mean", zero_infinity: bool = True):
+    def __init__(self, blank_token: int = 0, reduction: str = "mean", zero_infinity: bool = True, *,
+                 differentiable: bool = False):
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise ValueError(f"CTCLoss: {reduction} is not a valid value for reduction")
         self.blank_token = blank_token
         self.reduction = reduction
         self.zero_infinity = zero_infinity
+        self.differentiable = differentiable
 
     def forward(self, logits: torch.Tensor, targets: torch.Tensor, input_lengths: torch.Tensor,
                 target_lengths: torch.Tensor) -> torch.Tensor:
@@ -46,18 +83,30 @@ class CTCLoss(nn.Module):
         training.py:95-99); input_lengths, target_lengths (B,) on the device or the host."""
         from .decode import _on_device
 
-        if logits.requires_grad and torch.is_grad_enabled():
+        with_grad = logits.requires_grad and torch.is_grad_enabled()
+        if with_grad and not self.differentiable:
             raise RuntimeError(
                 "velocity_asr.training.CTCLoss is forward-only (evaluation): it has no backward pass. "
                 "Call it under torch.no_grad() or on detached logits.")
         if logits.dim() != 3:
             raise ValueError("CTCLoss: logits must be (batch, seq_len, vocab_size)")
-        logits = _on_device(logits.detach())
         B = logits.shape[0]
         if targets.dim() == 1:
             targets = self._pad_concatenated(targets, target_lengths, B)
-        emis, tg, frames, tlen = ops.ctc_emissions(logits, targets, input_lengths, target_lengths, self.blank_token)
-        nll = ops.ctc_loss(emis, tg, frames, tlen)
+        if with_grad:
+            # the casts to the device and to float32 are autograd's: the gradient comes back in the
+            # logits' own device, dtype and shape
+            logits = _on_device(logits)
+            dev = logits.device
+            tg = ops._ctc_targets("CTCLoss", targets, B, dev)
+            frames = ops._ctc_lengths("CTCLoss.input_lengths", input_lengths, B, dev, logits.shape[1])
+            tlen = ops._ctc_lengths("CTCLoss.target_lengths", target_lengths, B, dev, tg.shape[1])
+            nll = _CTCNll.apply(logits, tg, frames, tlen, self.blank_token, self.zero_infinity)
+        else:
+            logits = _on_device(logits.detach())
+            emis, tg, frames, tlen = ops.ctc_emissions(logits, targets, input_lengths, target_lengths,
+                                                       self.blank_token)
+            nll = ops.ctc_loss(emis, tg, frames, tlen)
         if self.zero_infinity:
             nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
         if self.reduction == "none":
