@@ -233,6 +233,47 @@ int64_t vasr_ssm_scan_workspace_floats(int B, int L, int Di, int N);
  * for hosts that choose between the streaming and chunked entry points (ABI 15). */
 int vasr_ssm_scan_split_selected(int B, int L, int Di, int N);
 
+/* ------------------------------------------------------------------ selective scan, backward (added to ABI 20)
+ * Training through the true recurrence (mode 1; reference ssm.py:134-171 under autograd, the
+ * operator mamba_ssm.selective_scan_fn differentiates, ssm.py:297-337).  With g = d loss / d out,
+ * s = sigmoid(z), gy = g silu(z) (gy = g without z), a_t = exp(dt_t A), and walking t down from
+ * L - 1 with gh_L = 0:
+ *   dz_t  = g_t y_t s (1 + z (1 - s)),          gh_t[d][n] = gy_t[d] C_t[n] + a_{t+1} gh_{t+1},
+ *   dC_t[n] = sum_d gy_t h_t,                   dB_t[n] = sum_d gh_t dt_t x_t,
+ *   dx_t  = gy_t D + dt_t sum_n gh_t B_t,       ddt_t = x_t sum_n gh_t B_t + sum_n gh_t a_t h_{t-1} A[n],
+ *   dA[n] = sum_{b,t,d} gh_t a_t h_{t-1} dt_t,  dD[d] = sum_{b,t} gy_t x_t.
+ * Limits are vasr_ssm_scan_f32's: fp32, N in {16, 32, 64, 128} (pad as there), L <= 8192, whole
+ * batches; Di a multiple of 1024 / N.  The scan is causal, so zero rows of g on padded frames give
+ * the exact gradients of a ragged batch.
+ *
+ * vasr_ssm_scan_save_f32: the forward.  Operands as vasr_ssm_scan_f32 at mode 1; gated = 0 reads
+ * no z (xz holds x alone, ld_xz >= Di) and writes out = y + x D.  out is bitwise
+ * vasr_ssm_scan_f32(mode 1)'s (gated = 0: that kernel's value before the gate).  ckpt receives the
+ * state h every 16-step chunk starts from, (B, ceil(L / 16), Di, N) floats =
+ * vasr_ssm_scan_checkpoint_floats(B, L, Di, N), 16-byte aligned.
+ *
+ * vasr_ssm_scan_bwd_f32: the reverse-time walk from those checkpoints.  x, z, dt, g: (B L, Di) row
+ * views with row strides ld_*; z and dz are both NULL for the ungated form; A = -exp(A_log) and
+ * A2 = A log2(e), N floats each.  Outputs, all contiguous and every element written: dx, ddt, dz
+ * (B L, Di); dB, dC (B L, N); dA_part (B, Di, N) and dD_part (B, Di), whose sums over (b, d) and
+ * over b are dA and dD.  workspace: vasr_ssm_scan_bwd_workspace_floats(B, L, Di, N) floats (the
+ * per-workgroup dB / dC partial sums, 2 (B L) (Di N / 1024) N).  No floating-point atomics: every
+ * sum runs in a fixed order, so the gradients are run-to-run bitwise, and an utterance's rows do
+ * not depend on the rest of the batch. */
+int vasr_ssm_scan_save_f32(const float* xz, int64_t ld_xz, const float* dt, int64_t ld_dt,
+                           const float* bc, int64_t ld_bc, const float* A2, const float* D,
+                           float* out, int64_t ld_out, int B, int L, int Di, int N, int gated,
+                           float* ckpt, int64_t ckpt_floats, void* stream);
+int64_t vasr_ssm_scan_checkpoint_floats(int B, int L, int Di, int N);
+int vasr_ssm_scan_bwd_f32(const float* x, int64_t ld_x, const float* z, int64_t ld_z,
+                          const float* dt, int64_t ld_dt, const float* bc, int64_t ld_bc,
+                          const float* A, const float* A2, const float* D,
+                          const float* g, int64_t ld_g, const float* ckpt,
+                          float* dx, float* ddt, float* dz, float* dB, float* dC,
+                          float* dA_part, float* dD_part, float* workspace, int64_t workspace_floats,
+                          int B, int L, int Di, int N, void* stream);
+int64_t vasr_ssm_scan_bwd_workspace_floats(int B, int L, int Di, int N);
+
 /* ------------------------------------------------------------------ SSMBlock tail, fused
  * The tail of SSMBlock._forward_impl (ssm.py:415-425) in one launch for d_model D = 192 and
  * FFN width / d_inner E = 384:

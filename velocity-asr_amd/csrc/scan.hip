@@ -3,7 +3,6 @@
 #include "scan_kernels.h"
 
 namespace vasr {
-namespace {
 // Lane layout of the streaming kernel (see vasr_ssm_scan_f32): 2 state indices per lane below 512
 // waves at 4 per lane, unless vasr_set_option(VASR_OPT_SCAN_LANES, 2|4) forces one.  Shared by the
 // gated and ungated entry points: the layouts differ in the order of the y = sum_n h C sums.
@@ -12,7 +11,6 @@ bool streaming_two(int B, int Di, int N) {
     const long waves4 = (long)B * Di * N / 256;
     return npl_env == 2 || (npl_env != 4 && waves4 < 512);
 }
-}  // namespace
 }  // namespace vasr
 
 VASR_API int vasr_ssm_scan_f32(const float* xz, int64_t ld_xz, const float* dt, int64_t ld_dt, const float* bc,

@@ -322,14 +322,21 @@ struct TreeChunk {
     }
 };
 
+__device__ __forceinline__ float* ckpt_of(float* p) { return p; }
+
 // GATE = false: the ungated form for the z-in-tail block (vasr_ssm_scan_ungated_f32): out = y + x D,
 // no z slab staged (x | dt | bc only), no silu; the fused tail applies the gate (ssm_tail.hip).
-template <int N, int MODE, int MAXUP, int TC = T, bool GATE = true>
+// SAVE (mode 1 only; the checkpointing forward of the backward pass, scan_bwd.hip): one more argument,
+// float* ckpt, receives the state h every chunk starts from, ckpt[b][chunk][d][n] ((B, ceil(L / TC), Di,
+// N) floats).  The argument is a pack so that the plain kernels keep their signature and their code.
+template <int N, int MODE, int MAXUP, int TC = T, bool GATE = true, bool SAVE = false, class... CK>
 __global__ __launch_bounds__(256, TC != T ? VASR_SCAN_WAVES_TC32 : NPL == 4 ? (MAXUP <= 7 ? VASR_SCAN_WAVES : 2) : (MAXUP <= 7 ? VASR_SCAN_WAVES_NPL2 : 3))
 void ssm_scan_kernel(const float* __restrict__ xz, int64_t ld_xz, const float* __restrict__ dt, int64_t ld_dt,
                      const float* __restrict__ bc, int64_t ld_bc, const float* __restrict__ A2g,
-                     const float* __restrict__ Dg, float* __restrict__ out, int64_t ld_out, int B, int L, int Di) {
+                     const float* __restrict__ Dg, float* __restrict__ out, int64_t ld_out, int B, int L, int Di,
+                     CK... ck) {
 #pragma clang fp contract(off)
+    static_assert(SAVE ? MODE == 1 && sizeof...(CK) == 1 : sizeof...(CK) == 0, "checkpoints: the recurrence only");
     constexpr int G = N / NPL;       // lanes per channel
     constexpr int TPC = TC + 1;      // partial-sum tile row
     constexpr int DPW = 64 / G;      // channels per wave
@@ -517,6 +524,11 @@ void ssm_scan_kernel(const float* __restrict__ xz, int64_t ld_xz, const float* _
             }
             if (c + 1 < nchunks) merge_upper<MAXUP, FMA, log2_c(TC)>(st, up, cha, chb, c);
         } else {
+            if constexpr (SAVE) {  // h before this chunk's first step
+                float* cp = ckpt_of(ck...) + (((int64_t)b * nchunks + c) * Di + d0 + dl) * N + g * NPL;
+#pragma unroll
+                for (int p = 0; p < NP; ++p) *reinterpret_cast<f2*>(cp + 2 * p) = h[p];
+            }
             for (int i = 0; i < nvalid; ++i) {
                 const float xv = sm.xs[i * DPB + dl];
                 const float dv = sm.dts[i * DPB + dl];
@@ -593,6 +605,23 @@ void ssm_scan_kernel(const float* __restrict__ xz, int64_t ld_xz, const float* _
         o[4] = (int64_t)r1;
     }
 #endif
+}
+
+// The checkpointing forward of the recurrence (vasr_ssm_scan_save_f32): the mode-1 kernel launch_n
+// runs, with SAVE.
+template <int N, bool GATE>
+int launch_save_n(const float* xz, int64_t ld_xz, const float* dt, int64_t ld_dt, const float* bc, int64_t ld_bc,
+                  const float* A2, const float* D, float* out, int64_t ld_out, int B, int L, int Di, float* ckpt,
+                  hipStream_t s) {
+    constexpr int G = N / NPL;
+    constexpr int DPB = NW * (64 / G);
+    if (Di % DPB != 0) {
+        set_error("vasr_ssm_scan_save_f32: Di=%d must be a multiple of %d for N=%d", Di, DPB, N);
+        return VASR_EUNSUPPORTED;
+    }
+    hipLaunchKernelGGL((ssm_scan_kernel<N, 1, 5, T, GATE, true, float*>), dim3(B * (Di / DPB)), dim3(64 * NW), 0, s, xz,
+                       ld_xz, dt, ld_dt, bc, ld_bc, A2, D, out, ld_out, B, L, Di, ckpt);
+    return launch_status("vasr_ssm_scan_save_f32");
 }
 
 template <int N, int MODE, bool GATE = true>

@@ -298,6 +298,9 @@ VASR_SCAN_LAUNCHERS(32)
 VASR_SCAN_LAUNCHERS(64)
 VASR_SCAN_LAUNCHERS(128)
 #undef VASR_SCAN_LAUNCHERS
+// scan.hip: the streaming kernel's lane layout for a launch (true = 2 state indices per lane);
+// the checkpointing forward (scan_bwd.hip) takes the same one, so its out is bitwise the same
+bool streaming_two(int B, int Di, int N);
 // One-launch time-split form (2 state indices per lane; N <= 64)
 #define VASR_SCAN_SPLIT_LAUNCHER(NN)                                                                               \
     int scan_split_n##NN(int mode, const float* xz, int64_t ld_xz, const float* dt, int64_t ld_dt, const float* bc, \

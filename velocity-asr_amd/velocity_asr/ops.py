@@ -592,6 +592,109 @@ def ssm_scan_ungated(x: torch.Tensor, dt: torch.Tensor, bc: torch.Tensor, A2: to
     return out
 
 
+SCAN_BWD_CHUNK = 16  # time steps per checkpoint of ssm_scan_save (include/vasr.h)
+
+
+def scan_bwd_channels(N: int) -> int:
+    """Channels per workgroup of the scan's backward kernel at kernel state dim N: Di must be a
+    multiple (4 state indices per lane: 1024 / N)."""
+    return 1024 // N
+
+
+def ssm_scan_save(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, bc: torch.Tensor, A2: torch.Tensor,
+                  D: torch.Tensor, B: int, Lq: int):
+    """The recurrence's forward that keeps what its backward needs (vasr_ssm_scan_save_f32).
+    x, dt (B*L, Di) and bc (B*L, 2N) [B|C] row views; z: the other half of x's rows (x and z are
+    views [:, :Di] and [:, Di:] of one (B*L, 2Di) tensor, as in_proj writes them) or None for the
+    ungated form.  Returns (out (B*L, Di), ckpt (B, ceil(L / 16), Di, N)): out bitwise
+    ssm_scan(mode=1)'s (ungated: its value before the gate), ckpt the state every chunk starts from."""
+    D = f32(D)
+    for n, t in (("x", x), ("dt", dt), ("bc", bc), ("A2", A2), ("D", D)) + ((("z", z),) if z is not None else ()):
+        _cuda_f32(f"ssm_scan_save.{n}", t)
+    M, Di, ld_xz = _rows("ssm_scan_save.x", x)
+    _, Di2, ld_dt = _rows("ssm_scan_save.dt", dt)
+    _, two_n, ld_bc = _rows("ssm_scan_save.bc", bc)
+    N = A2.numel()
+    if M != B * Lq or Di2 != Di or two_n != 2 * N or D.numel() != Di or N not in SCAN_STATE_DIMS:
+        raise ValueError("ssm_scan_save: inconsistent shapes")
+    if z is not None:
+        _, Dz, ld_z = _rows("ssm_scan_save.z", z)
+        if Dz != Di or z.shape[0] != M or ld_z != ld_xz or z.data_ptr() != x.data_ptr() + 4 * Di:
+            raise ValueError("ssm_scan_save: x and z must be the two halves of one (B*L, 2Di) tensor")
+        ld_xz = max(ld_xz, 2 * Di)  # a single row reports its own width
+    out = torch.empty((M, Di), device=x.device, dtype=torch.float32)
+    nck = int(L.lib().vasr_ssm_scan_checkpoint_floats(B, Lq, Di, N))
+    ckpt = torch.empty(nck, device=x.device, dtype=torch.float32)
+    ev = _t0("ssm_scan_save")
+    check(L.lib().vasr_ssm_scan_save_f32(x.data_ptr(), ld_xz, dt.data_ptr(), ld_dt, bc.data_ptr(), ld_bc, A2.data_ptr(),
+                                         D.data_ptr(), out.data_ptr(), Di, B, Lq, Di, N, int(z is not None),
+                                         ckpt.data_ptr(), ckpt.numel(), stream_of(x)), "vasr_ssm_scan_save_f32")
+    _t1("ssm_scan_save", ev, dict(B=B, L=Lq, Di=Di, N=N, gated=z is not None))
+    return out, ckpt.view(B, -1, Di, N) if nck else ckpt.view(B, 0, Di, N)
+
+
+def ssm_scan_bwd(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, bc: torch.Tensor, A: torch.Tensor,
+                 A2: torch.Tensor, D: torch.Tensor, g: torch.Tensor, ckpt: torch.Tensor, B: int, Lq: int,
+                 out: Optional[dict] = None, workspace: Optional[torch.Tensor] = None):
+    """The recurrence's backward (vasr_ssm_scan_bwd_f32) from ssm_scan_save's checkpoints: g (B*L, Di)
+    = d loss / d out.  Returns a dict: dx, ddt, dz (None without z) (B*L, Di); dB, dC (B*L, N);
+    dA_part (B, Di, N) and dD_part (B, Di), the per-(utterance, channel) sums whose totals over
+    (b, d) and over b are dA and dD.  Every sum runs in a fixed order (no atomics): run-to-run
+    bitwise, and an utterance's rows do not depend on the rest of the batch.  out / workspace:
+    preallocated outputs (the same keys) and partial-sum workspace."""
+    D = f32(D)
+    ops_ = (("x", x), ("dt", dt), ("bc", bc), ("A", A), ("A2", A2), ("D", D), ("g", g), ("ckpt", ckpt))
+    for n, t in ops_ + ((("z", z),) if z is not None else ()):
+        _cuda_f32(f"ssm_scan_bwd.{n}", t)
+    M, Di, ld_x = _rows("ssm_scan_bwd.x", x)
+    _, Di2, ld_dt = _rows("ssm_scan_bwd.dt", dt)
+    _, Di3, ld_g = _rows("ssm_scan_bwd.g", g)
+    _, two_n, ld_bc = _rows("ssm_scan_bwd.bc", bc)
+    N = A2.numel()
+    if (M != B * Lq or Di2 != Di or Di3 != Di or g.shape[0] != M or two_n != 2 * N or A.numel() != N
+            or D.numel() != Di or N not in SCAN_STATE_DIMS):
+        raise ValueError("ssm_scan_bwd: inconsistent shapes")
+    if Di % scan_bwd_channels(N):
+        raise ValueError(f"ssm_scan_bwd: Di={Di} must be a multiple of {scan_bwd_channels(N)} at N={N}")
+    ld_z = 0
+    if z is not None:
+        _, Dz, ld_z = _rows("ssm_scan_bwd.z", z)
+        if Dz != Di or z.shape[0] != M:
+            raise ValueError("ssm_scan_bwd: inconsistent shapes")
+    nck = int(L.lib().vasr_ssm_scan_checkpoint_floats(B, Lq, Di, N))
+    if ckpt.numel() != nck or not ckpt.is_contiguous():
+        raise ValueError(f"ssm_scan_bwd: ckpt must be ssm_scan_save's ({nck} floats)")
+    dev = x.device
+    if out is None:
+        out = dict(dx=torch.empty((M, Di), device=dev), ddt=torch.empty((M, Di), device=dev),
+                   dz=torch.empty((M, Di), device=dev) if z is not None else None,
+                   dB=torch.empty((M, N), device=dev), dC=torch.empty((M, N), device=dev),
+                   dA_part=torch.empty((B, Di, N), device=dev), dD_part=torch.empty((B, Di), device=dev))
+    for k, shape in (("dx", (M, Di)), ("ddt", (M, Di)), ("dz", (M, Di)), ("dB", (M, N)), ("dC", (M, N)),
+                     ("dA_part", (B, Di, N)), ("dD_part", (B, Di))):
+        t = out[k]
+        if k == "dz" and z is None:
+            if t is not None:
+                raise ValueError("ssm_scan_bwd: dz without z")
+            continue
+        _cuda_f32(f"ssm_scan_bwd.{k}", t)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"ssm_scan_bwd: {k} must be contiguous {shape}")
+    nws = int(L.lib().vasr_ssm_scan_bwd_workspace_floats(B, Lq, Di, N))
+    if workspace is None:
+        workspace = torch.empty(nws, device=dev, dtype=torch.float32)
+    _cuda_f32("ssm_scan_bwd.workspace", workspace)
+    ev = _t0("ssm_scan_bwd")
+    check(L.lib().vasr_ssm_scan_bwd_f32(x.data_ptr(), ld_x, ptr(z), ld_z, dt.data_ptr(), ld_dt, bc.data_ptr(), ld_bc,
+                                        A.data_ptr(), A2.data_ptr(), D.data_ptr(), g.data_ptr(), ld_g, ckpt.data_ptr(),
+                                        out["dx"].data_ptr(), out["ddt"].data_ptr(), ptr(out["dz"]),
+                                        out["dB"].data_ptr(), out["dC"].data_ptr(), out["dA_part"].data_ptr(),
+                                        out["dD_part"].data_ptr(), workspace.data_ptr(), workspace.numel(), B, Lq, Di,
+                                        N, stream_of(x)), "vasr_ssm_scan_bwd_f32")
+    _t1("ssm_scan_bwd", ev, dict(B=B, L=Lq, Di=Di, N=N, gated=z is not None))
+    return out
+
+
 def ssm_block_tail_gated(yd: torch.Tensor, u: torch.Tensor, wz: torch.Tensor, mode: int, x: torch.Tensor,
                          wo: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, ln_eps: float, w1: torch.Tensor,
                          b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,

@@ -9,7 +9,9 @@ unchanged.  Forward passes run the HIP kernels of libvasr_hip.so:
              -> gated selective scan (tree or recurrence) with D skip and y*silu(z) fused
              -> out_proj GEMM with the residual add fused
              -> LN2 -> FFN1 GEMM + GELU -> FFN2 GEMM + bias + residual
-Inference only: dropout is the identity (as in eval()), no autograd.
+Inference only: dropout is the identity (as in eval()), no autograd -- except selective_scan and
+SelectiveSSM.forward_differentiable, the scan of scan_mode "sequential" / "mamba" as an autograd
+operator with a HIP backward pass.
 """
 
 from __future__ import annotations
@@ -57,6 +59,122 @@ def _check_eval(module: nn.Module) -> None:
         _warned_training = True
         warnings.warn("velocity_asr (MI355X build) is inference-only: dropout is treated as identity; "
                       "call model.eval() to silence this warning", stacklevel=3)
+
+
+def _scan_operands(x, dt, A, B, C, D, z):
+    """Validate selective_scan's arguments (ValueError) and return (batch, L, Di, N)."""
+    names = (("x", x, 3), ("dt", dt, 3), ("A", A, 1), ("B", B, 3), ("C", C, 3), ("D", D, 1)) + (
+        (("z", z, 3),) if z is not None else ())
+    for n, t, rank in names:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"selective_scan: {n} must be a tensor")
+        if t.dim() != rank:
+            raise ValueError(f"selective_scan: {n} must have {rank} dimensions, got shape {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"selective_scan: {n} must be float32, got {t.dtype} (the operator is fp32 only)")
+    batch, L, Di = x.shape
+    N = A.shape[0]
+    want = dict(dt=(batch, L, Di), B=(batch, L, N), C=(batch, L, N), D=(Di,), z=(batch, L, Di))
+    for n, t, _ in names:
+        if n in want and tuple(t.shape) != want[n]:
+            raise ValueError(f"selective_scan: {n} has shape {tuple(t.shape)}, expected {want[n]}")
+    if N < 1 or L > 8192:
+        raise ValueError(f"selective_scan: state dim {N} / length {L} out of range (N >= 1, L <= 8192)")
+    return batch, L, Di, N
+
+
+def _pad_states(B, C, A, N, Np):
+    """[B | C] rows (M, 2 Np) and A (Np,) with the state dim zero-padded to the kernel's (ops.ssm_scan's
+    rule: A = 0, B = C = 0 there, so the padded states stay exactly 0)."""
+    M = B.shape[0] * B.shape[1]
+    Bm, Cm = B.reshape(M, N), C.reshape(M, N)
+    if Np == N:
+        return torch.cat([Bm, Cm], 1), A.contiguous()
+    pad = torch.zeros((M, Np - N), device=B.device, dtype=B.dtype)
+    return torch.cat([Bm, pad, Cm, pad], 1), torch.cat([A, torch.zeros(Np - N, device=A.device, dtype=A.dtype)])
+
+
+class _SelectiveScan(torch.autograd.Function):
+    """out = selective scan (the true recurrence) with gradients to all seven inputs.  Forward:
+    ops.ssm_scan_save (the mode-1 kernel, also keeping the state at every 16-step chunk boundary).
+    Backward: ops.ssm_scan_bwd, the reverse-time walk from those checkpoints; dA and dD are the sums
+    of its per-(utterance, channel) partials.  Enqueued on the current stream, no host sync."""
+
+    @staticmethod
+    def forward(ctx, x, dt, A, B, C, D, z):
+        batch, L, Di, N = _scan_operands(x, dt, A, B, C, D, z)
+        Np = ops.scan_state_dim(N)
+        M = batch * L
+        with torch.no_grad():
+            if z is not None:
+                xz = torch.cat([x.reshape(M, Di), z.reshape(M, Di)], 1)
+                xs, zs = xz[:, :Di], xz[:, Di:]
+            else:
+                xs, zs = x.reshape(M, Di).contiguous(), None
+            dts = dt.reshape(M, Di).contiguous()
+            bc, Ap = _pad_states(B, C, A, N, Np)
+            A2 = Ap * torch.tensor(ops.LOG2E, dtype=torch.float32)
+            Dc = D.contiguous()
+            out, ckpt = ops.ssm_scan_save(xs, zs, dts, bc, A2, Dc, batch, L)
+        ctx.save_for_backward(xs, dts, bc, Ap, A2, Dc, ckpt, *(() if zs is None else (zs,)))
+        ctx.dims = (batch, L, Di, N)
+        return out.view(batch, L, Di)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xs, dts, bc, Ap, A2, Dc, ckpt, *rest = ctx.saved_tensors
+        zs = rest[0] if rest else None
+        batch, L, Di, N = ctx.dims
+        r = ops.ssm_scan_bwd(xs, zs, dts, bc, Ap, A2, Dc, g.to(torch.float32).reshape(batch * L, Di).contiguous(),
+                             ckpt, batch, L)
+        need = ctx.needs_input_grad
+        return (r["dx"].view(batch, L, Di) if need[0] else None,
+                r["ddt"].view(batch, L, Di) if need[1] else None,
+                r["dA_part"].sum(dim=(0, 1))[:N] if need[2] else None,
+                r["dB"][:, :N].reshape(batch, L, N) if need[3] else None,
+                r["dC"][:, :N].reshape(batch, L, N) if need[4] else None,
+                r["dD_part"].sum(dim=0) if need[5] else None,
+                r["dz"].view(batch, L, Di) if zs is not None and need[6] else None)
+
+
+_UNIT_GATE = 128.0  # silu(128) == 128 exactly in fp32 (exp(-128) rounds to 0): y * 128 / 128 is y, bitwise
+
+
+def selective_scan(x: torch.Tensor, dt: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor,
+                   D: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The selective scan as a differentiable operator: the reference's SelectiveSSM._sequential_scan
+    (ssm.py:134-171) with the D skip, times silu(z) when z is given -- what mamba_ssm's
+    selective_scan_fn computes for a state matrix shared across channels.
+
+        h_t = exp(dt_t A) h_{t-1} + dt_t x_t B_t,   out_t = (sum_n h_t C_t + x_t D) [* silu(z_t)]
+
+    x, dt, z: (batch, L, Di); A: (N,); B, C: (batch, L, N); D: (Di,); float32 on a HIP device.  All
+    seven inputs get gradients from the HIP backward kernel (vasr_ssm_scan_bwd_f32); the forward
+    value is bitwise the inference kernel's (ops.ssm_scan, mode 1).  When nothing requires grad the
+    inference kernel itself runs and no checkpoint is written.  A state dim without a kernel
+    instance (e.g. 48) runs zero-padded to the next one and dA, dB, dC are sliced back.  Di must be
+    a multiple of 1024 / N' channels (N' the kernel state dim), L <= 8192.
+
+    Batches are full-length.  The scan is causal, so for a padded batch zero the upstream gradient
+    on the padded frames: the gradients of the valid frames and of the parameters are then exact."""
+    batch, L, Di, N = _scan_operands(x, dt, A, B, C, D, z)
+    _lib.require_device()
+    Np = ops.scan_state_dim(N)
+    if Di % ops.scan_bwd_channels(Np):
+        raise ValueError(f"selective_scan: Di={Di} must be a multiple of {ops.scan_bwd_channels(Np)} at state dim {N}")
+    args = (x, dt, A, B, C, D) + ((z,) if z is not None else ())
+    if torch.is_grad_enabled() and any(t.requires_grad for t in args):
+        return _SelectiveScan.apply(x, dt, A, B, C, D, z)
+    M = batch * L
+    gate = z.reshape(M, Di) if z is not None else torch.full((M, Di), _UNIT_GATE, device=x.device)
+    xz = torch.cat([x.detach().reshape(M, Di), gate.detach()], 1)
+    bc, Ap = _pad_states(B.detach(), C.detach(), A.detach(), N, Np)
+    A2 = Ap * torch.tensor(ops.LOG2E, dtype=torch.float32)
+    out = ops.ssm_scan(xz, dt.detach().reshape(M, Di).contiguous(), bc, A2, D.detach().contiguous(), batch, L, 1)
+    if z is None:
+        out = out / _UNIT_GATE  # the unit gate divided out: exact (a power of two)
+    return out.view(batch, L, Di)
 
 
 class SelectiveSSM(nn.Module):
@@ -173,6 +291,25 @@ class SelectiveSSM(nn.Module):
         B, L, _ = x.shape
         g = self.gated_scan(x.reshape(B * L, -1), B, L)
         return ops.gemm(g, self.out_proj.weight).view(B, L, self.d_model)
+
+    def forward_differentiable(self, x: torch.Tensor) -> torch.Tensor:
+        """The reference's forward (ssm.py:92-132) for training: the projections, softplus and
+        A = -exp(A_log) as torch ops on this module's parameters (torch.autograd differentiates
+        them), the scan as selective_scan (HIP forward and backward), then out_proj.  loss.backward()
+        reaches all six parameters and x.  scan_mode "sequential" and "mamba" only: "parallel"
+        reproduces the reference's mis-combined tree, a different function of its inputs whose
+        gradient the recurrence's backward kernel does not compute."""
+        if _SCAN_MODE_ID[self.scan_mode] != 1:
+            raise NotImplementedError(
+                f"SelectiveSSM.forward_differentiable: scan_mode={self.scan_mode!r} is the reference's tree scan, "
+                "which is not the recurrence the backward kernel differentiates; use 'sequential' or 'mamba'")
+        F = torch.nn.functional
+        xp, z = F.linear(x, self.in_proj.weight).chunk(2, dim=-1)
+        Bm, Cm = F.linear(xp, self.x_proj.weight).chunk(2, dim=-1)
+        dt = F.softplus(F.linear(xp, self.dt_proj.weight, self.dt_proj.bias))
+        A = -torch.exp(self.A_log)
+        y = selective_scan(xp, dt, A, Bm, Cm, self.D, z)
+        return F.linear(y, self.out_proj.weight)
 
 
 class SSMBlock(nn.Module):

@@ -5,9 +5,12 @@ metrics scripts/evaluate.py imports (training.py:412-501).
 CTCLoss here is the loss on the HIP path (vasr_ctc_emissions_f32 + vasr_ctc_loss_f32): by default
 forward only, scoring a known transcript; with differentiable=True it also has a backward pass
 (vasr_ctc_loss_alpha_f32 in the forward, vasr_ctc_occupancy_f32 + vasr_ctc_grad_logits_f32 in the
-backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.CTCLoss.  The
-rest of training (backward passes of the model's kernels, schedulers, Trainer) stays outside this
-inference build's scope.
+backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.CTCLoss.  Of the
+model's own kernels the selective scan's recurrence has a backward pass too (velocity_asr.ssm.selective_scan,
+SelectiveSSM.forward_differentiable: vasr_ssm_scan_save_f32 + vasr_ssm_scan_bwd_f32); the layers around it
+are GEMM, LayerNorm, conv and attention, which torch.autograd differentiates as torch ops.  The rest of
+training (backward passes of the fused GEMM, tail and LayerNorm kernels, the tree scan modes, schedulers,
+Trainer) stays outside this build's scope.
 """
 
 from __future__ import annotations
