@@ -274,6 +274,37 @@ int vasr_ssm_scan_bwd_f32(const float* x, int64_t ld_x, const float* z, int64_t 
                           int B, int L, int Di, int N, void* stream);
 int64_t vasr_ssm_scan_bwd_workspace_floats(int B, int L, int Di, int N);
 
+/* ------------------------------------------------------------------ tree scan, backward (added to ABI 20)
+ * Training through the default scan (modes 0 / 2: the reference's _parallel_scan under autograd,
+ * ssm.py:173-295), a different function of its inputs from the recurrence.  Per (utterance,
+ * channel, state n): a_t = exp(dt_t A[n]), b_t = x_t dt_t B_t[n], P_e = prod_{r <= e} a_r, and for
+ * an aligned block S of 2^k steps ending at e_S, R_S = its local inclusive scan.  The state is
+ *   h_t = sum over the set bits k of t of P_{e_S} R_S,  S = [t with bits 0..k cleared, + 2^k),
+ * and with gh_t = gy_t C_t[n], w_S = P_{e_S} sum_{t in the right sibling of S} gh_t and
+ * lambda_S(s) = w_S prod_{s < r <= e_S} a_r the gradients are
+ *   d/db_s = sum_{S containing s} lambda_S(s),
+ *   d/d(dt_r A[n]) = sum_{S : e_S >= r} w_S R_S + sum_{S containing r} lambda_S(r - 1) rho^S_{r-1}
+ * (rho^S_r: the local scan of S up to r; nothing divides by a_r), from which dx, ddt, dz, dB, dC,
+ * dA, dD follow as for the recurrence.  The forward is vasr_ssm_scan_f32 / vasr_ssm_scan_ungated_f32
+ * itself (only the inputs are kept); modes 0 and 2 round differently and share this gradient.
+ *
+ * vasr_ssm_tree_bwd_f32: operands, outputs, limits and guarantees as vasr_ssm_scan_bwd_f32, without
+ * checkpoints: x, z, dt, g (B L, Di) row views, z and dz both NULL for the ungated form, bc
+ * (B L, 2N) [B | C], A and A2 = A log2(e); dx, ddt, dz (B L, Di), dB, dC (B L, N), dA_part
+ * (B, Di, N), dD_part (B, Di), every element written; N in {16, 32, 64, 128}, Di a multiple of
+ * 1024 / N, L <= 8192.  workspace: vasr_ssm_tree_bwd_workspace_floats(B, L, Di, N) floats, 16-byte
+ * aligned: B ceil(L / 16) Di (7 N + 1), seven floats per 16-step chunk, channel and state plus the
+ * chunk's dD partial -- no (B, L, Di, N) array is formed.  No atomics: run-to-run bitwise, and an
+ * utterance's rows do not depend on the rest of the batch. */
+int vasr_ssm_tree_bwd_f32(const float* x, int64_t ld_x, const float* z, int64_t ld_z,
+                          const float* dt, int64_t ld_dt, const float* bc, int64_t ld_bc,
+                          const float* A, const float* A2, const float* D,
+                          const float* g, int64_t ld_g,
+                          float* dx, float* ddt, float* dz, float* dB, float* dC,
+                          float* dA_part, float* dD_part, float* workspace, int64_t workspace_floats,
+                          int B, int L, int Di, int N, void* stream);
+int64_t vasr_ssm_tree_bwd_workspace_floats(int B, int L, int Di, int N);
+
 /* ------------------------------------------------------------------ SSMBlock tail, fused
  * The tail of SSMBlock._forward_impl (ssm.py:415-425) in one launch for d_model D = 192 and
  * FFN width / d_inner E = 384:

@@ -76,6 +76,9 @@ _SIGNATURES = {
     "vasr_ssm_scan_bwd_f32": ([c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64] + [c_p] * 9
                               + [c_i64] + [ctypes.c_int] * 4 + [c_p], ctypes.c_int),
     "vasr_ssm_scan_bwd_workspace_floats": ([ctypes.c_int] * 4, c_i64),
+    "vasr_ssm_tree_bwd_f32": ([c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64] + [c_p] * 8
+                              + [c_i64] + [ctypes.c_int] * 4 + [c_p], ctypes.c_int),
+    "vasr_ssm_tree_bwd_workspace_floats": ([ctypes.c_int] * 4, c_i64),
     "vasr_ssm_scan_split_selected": ([ctypes.c_int] * 4, ctypes.c_int),
     "vasr_ssm_block_tail_f32": ([c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64]
                                 + [ctypes.c_int] * 3 + [c_p], ctypes.c_int),

@@ -633,37 +633,33 @@ def ssm_scan_save(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, 
     return out, ckpt.view(B, -1, Di, N) if nck else ckpt.view(B, 0, Di, N)
 
 
-def ssm_scan_bwd(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, bc: torch.Tensor, A: torch.Tensor,
-                 A2: torch.Tensor, D: torch.Tensor, g: torch.Tensor, ckpt: torch.Tensor, B: int, Lq: int,
-                 out: Optional[dict] = None, workspace: Optional[torch.Tensor] = None):
-    """The recurrence's backward (vasr_ssm_scan_bwd_f32) from ssm_scan_save's checkpoints: g (B*L, Di)
-    = d loss / d out.  Returns a dict: dx, ddt, dz (None without z) (B*L, Di); dB, dC (B*L, N);
-    dA_part (B, Di, N) and dD_part (B, Di), the per-(utterance, channel) sums whose totals over
-    (b, d) and over b are dA and dD.  Every sum runs in a fixed order (no atomics): run-to-run
-    bitwise, and an utterance's rows do not depend on the rest of the batch.  out / workspace:
-    preallocated outputs (the same keys) and partial-sum workspace."""
+def _ssm_bwd(tag: str, x, z, dt, bc, A, A2, D, g, ckpt, B: int, Lq: int, out, workspace):
+    """ssm_scan_bwd (ckpt given) and ssm_tree_bwd (ckpt None): the checks, the output dict and the call."""
+    tree = ckpt is None
+    entry = "vasr_ssm_tree_bwd" if tree else "vasr_ssm_scan_bwd"
     D = f32(D)
-    ops_ = (("x", x), ("dt", dt), ("bc", bc), ("A", A), ("A2", A2), ("D", D), ("g", g), ("ckpt", ckpt))
+    ops_ = (("x", x), ("dt", dt), ("bc", bc), ("A", A), ("A2", A2), ("D", D), ("g", g)) + (() if tree else (("ckpt", ckpt),))
     for n, t in ops_ + ((("z", z),) if z is not None else ()):
-        _cuda_f32(f"ssm_scan_bwd.{n}", t)
-    M, Di, ld_x = _rows("ssm_scan_bwd.x", x)
-    _, Di2, ld_dt = _rows("ssm_scan_bwd.dt", dt)
-    _, Di3, ld_g = _rows("ssm_scan_bwd.g", g)
-    _, two_n, ld_bc = _rows("ssm_scan_bwd.bc", bc)
+        _cuda_f32(f"{tag}.{n}", t)
+    M, Di, ld_x = _rows(f"{tag}.x", x)
+    _, Di2, ld_dt = _rows(f"{tag}.dt", dt)
+    _, Di3, ld_g = _rows(f"{tag}.g", g)
+    _, two_n, ld_bc = _rows(f"{tag}.bc", bc)
     N = A2.numel()
     if (M != B * Lq or Di2 != Di or Di3 != Di or g.shape[0] != M or two_n != 2 * N or A.numel() != N
             or D.numel() != Di or N not in SCAN_STATE_DIMS):
-        raise ValueError("ssm_scan_bwd: inconsistent shapes")
+        raise ValueError(f"{tag}: inconsistent shapes")
     if Di % scan_bwd_channels(N):
-        raise ValueError(f"ssm_scan_bwd: Di={Di} must be a multiple of {scan_bwd_channels(N)} at N={N}")
+        raise ValueError(f"{tag}: Di={Di} must be a multiple of {scan_bwd_channels(N)} at N={N}")
     ld_z = 0
     if z is not None:
-        _, Dz, ld_z = _rows("ssm_scan_bwd.z", z)
+        _, Dz, ld_z = _rows(f"{tag}.z", z)
         if Dz != Di or z.shape[0] != M:
-            raise ValueError("ssm_scan_bwd: inconsistent shapes")
-    nck = int(L.lib().vasr_ssm_scan_checkpoint_floats(B, Lq, Di, N))
-    if ckpt.numel() != nck or not ckpt.is_contiguous():
-        raise ValueError(f"ssm_scan_bwd: ckpt must be ssm_scan_save's ({nck} floats)")
+            raise ValueError(f"{tag}: inconsistent shapes")
+    if not tree:
+        nck = int(L.lib().vasr_ssm_scan_checkpoint_floats(B, Lq, Di, N))
+        if ckpt.numel() != nck or not ckpt.is_contiguous():
+            raise ValueError(f"{tag}: ckpt must be ssm_scan_save's ({nck} floats)")
     dev = x.device
     if out is None:
         out = dict(dx=torch.empty((M, Di), device=dev), ddt=torch.empty((M, Di), device=dev),
@@ -675,24 +671,47 @@ def ssm_scan_bwd(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, b
         t = out[k]
         if k == "dz" and z is None:
             if t is not None:
-                raise ValueError("ssm_scan_bwd: dz without z")
+                raise ValueError(f"{tag}: dz without z")
             continue
-        _cuda_f32(f"ssm_scan_bwd.{k}", t)
+        _cuda_f32(f"{tag}.{k}", t)
         if tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"ssm_scan_bwd: {k} must be contiguous {shape}")
-    nws = int(L.lib().vasr_ssm_scan_bwd_workspace_floats(B, Lq, Di, N))
+            raise ValueError(f"{tag}: {k} must be contiguous {shape}")
+    nws = int(getattr(L.lib(), entry + "_workspace_floats")(B, Lq, Di, N))
     if workspace is None:
         workspace = torch.empty(nws, device=dev, dtype=torch.float32)
-    _cuda_f32("ssm_scan_bwd.workspace", workspace)
-    ev = _t0("ssm_scan_bwd")
-    check(L.lib().vasr_ssm_scan_bwd_f32(x.data_ptr(), ld_x, ptr(z), ld_z, dt.data_ptr(), ld_dt, bc.data_ptr(), ld_bc,
-                                        A.data_ptr(), A2.data_ptr(), D.data_ptr(), g.data_ptr(), ld_g, ckpt.data_ptr(),
-                                        out["dx"].data_ptr(), out["ddt"].data_ptr(), ptr(out["dz"]),
-                                        out["dB"].data_ptr(), out["dC"].data_ptr(), out["dA_part"].data_ptr(),
-                                        out["dD_part"].data_ptr(), workspace.data_ptr(), workspace.numel(), B, Lq, Di,
-                                        N, stream_of(x)), "vasr_ssm_scan_bwd_f32")
-    _t1("ssm_scan_bwd", ev, dict(B=B, L=Lq, Di=Di, N=N, gated=z is not None))
+    _cuda_f32(f"{tag}.workspace", workspace)
+    ev = _t0(tag)
+    check(getattr(L.lib(), entry + "_f32")(
+        x.data_ptr(), ld_x, ptr(z), ld_z, dt.data_ptr(), ld_dt, bc.data_ptr(), ld_bc, A.data_ptr(), A2.data_ptr(),
+        D.data_ptr(), g.data_ptr(), ld_g, *(() if tree else (ckpt.data_ptr(),)), out["dx"].data_ptr(),
+        out["ddt"].data_ptr(), ptr(out["dz"]), out["dB"].data_ptr(), out["dC"].data_ptr(), out["dA_part"].data_ptr(),
+        out["dD_part"].data_ptr(), workspace.data_ptr(), workspace.numel(), B, Lq, Di, N, stream_of(x)), entry + "_f32")
+    _t1(tag, ev, dict(B=B, L=Lq, Di=Di, N=N, gated=z is not None))
     return out
+
+
+def ssm_scan_bwd(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, bc: torch.Tensor, A: torch.Tensor,
+                 A2: torch.Tensor, D: torch.Tensor, g: torch.Tensor, ckpt: torch.Tensor, B: int, Lq: int,
+                 out: Optional[dict] = None, workspace: Optional[torch.Tensor] = None):
+    """The recurrence's backward (vasr_ssm_scan_bwd_f32) from ssm_scan_save's checkpoints: g (B*L, Di)
+    = d loss / d out.  Returns a dict: dx, ddt, dz (None without z) (B*L, Di); dB, dC (B*L, N);
+    dA_part (B, Di, N) and dD_part (B, Di), the per-(utterance, channel) sums whose totals over
+    (b, d) and over b are dA and dD.  Every sum runs in a fixed order (no atomics): run-to-run
+    bitwise, and an utterance's rows do not depend on the rest of the batch.  out / workspace:
+    preallocated outputs (the same keys) and partial-sum workspace."""
+    if ckpt is None:
+        raise ValueError("ssm_scan_bwd: ckpt must be ssm_scan_save's")
+    return _ssm_bwd("ssm_scan_bwd", x, z, dt, bc, A, A2, D, g, ckpt, B, Lq, out, workspace)
+
+
+def ssm_tree_bwd(x: torch.Tensor, z: Optional[torch.Tensor], dt: torch.Tensor, bc: torch.Tensor, A: torch.Tensor,
+                 A2: torch.Tensor, D: torch.Tensor, g: torch.Tensor, B: int, Lq: int,
+                 out: Optional[dict] = None, workspace: Optional[torch.Tensor] = None):
+    """The tree scan's backward (vasr_ssm_tree_bwd_f32; modes 0 / 2, scan_mode="parallel"): the
+    gradient of ssm_scan / ssm_scan_ungated at a tree mode from the inputs alone, no checkpoints.
+    Operands, the returned dict, out / workspace and the guarantees are ssm_scan_bwd's; the workspace
+    is vasr_ssm_tree_bwd_workspace_floats(B, L, Di, N) floats (7 per 16-step chunk, channel and state)."""
+    return _ssm_bwd("ssm_tree_bwd", x, z, dt, bc, A, A2, D, g, None, B, Lq, out, workspace)
 
 
 def ssm_block_tail_gated(yd: torch.Tensor, u: torch.Tensor, wz: torch.Tensor, mode: int, x: torch.Tensor,

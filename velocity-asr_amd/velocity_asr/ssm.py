@@ -9,9 +9,10 @@ unchanged.  Forward passes run the HIP kernels of libvasr_hip.so:
              -> gated selective scan (tree or recurrence) with D skip and y*silu(z) fused
              -> out_proj GEMM with the residual add fused
              -> LN2 -> FFN1 GEMM + GELU -> FFN2 GEMM + bias + residual
-Inference only: dropout is the identity (as in eval()), no autograd -- except selective_scan and
-SelectiveSSM.forward_differentiable, the scan of scan_mode "sequential" / "mamba" as an autograd
-operator with a HIP backward pass.
+forward() is inference only: dropout is the identity (as in eval()), no autograd.  Training goes
+through selective_scan -- either scan (the recurrence of "sequential" / "mamba", the tree of the
+default "parallel") as an autograd operator with a HIP backward pass -- and the modules'
+forward_differentiable (SelectiveSSM, SSMBlock, LocalSSMProcessor, GlobalSSM).
 """
 
 from __future__ import annotations
@@ -94,6 +95,18 @@ def _pad_states(B, C, A, N, Np):
     return torch.cat([Bm, pad, Cm, pad], 1), torch.cat([A, torch.zeros(Np - N, device=A.device, dtype=A.dtype)])
 
 
+def _input_grads(r, need, batch, L, Di, N):
+    """ops.ssm_scan_bwd's / ops.ssm_tree_bwd's dict as the gradients of (x, dt, A, B, C, D, z): dA and dD summed
+    from their per-(utterance, channel) partials, a padded state dim sliced back, None where not needed."""
+    return (r["dx"].view(batch, L, Di) if need[0] else None,
+            r["ddt"].view(batch, L, Di) if need[1] else None,
+            r["dA_part"].sum(dim=(0, 1))[:N] if need[2] else None,
+            r["dB"][:, :N].reshape(batch, L, N) if need[3] else None,
+            r["dC"][:, :N].reshape(batch, L, N) if need[4] else None,
+            r["dD_part"].sum(dim=0) if need[5] else None,
+            r["dz"].view(batch, L, Di) if r["dz"] is not None and need[6] else None)
+
+
 class _SelectiveScan(torch.autograd.Function):
     """out = selective scan (the true recurrence) with gradients to all seven inputs.  Forward:
     ops.ssm_scan_save (the mode-1 kernel, also keeping the state at every 16-step chunk boundary).
@@ -128,21 +141,60 @@ class _SelectiveScan(torch.autograd.Function):
         batch, L, Di, N = ctx.dims
         r = ops.ssm_scan_bwd(xs, zs, dts, bc, Ap, A2, Dc, g.to(torch.float32).reshape(batch * L, Di).contiguous(),
                              ckpt, batch, L)
-        need = ctx.needs_input_grad
-        return (r["dx"].view(batch, L, Di) if need[0] else None,
-                r["ddt"].view(batch, L, Di) if need[1] else None,
-                r["dA_part"].sum(dim=(0, 1))[:N] if need[2] else None,
-                r["dB"][:, :N].reshape(batch, L, N) if need[3] else None,
-                r["dC"][:, :N].reshape(batch, L, N) if need[4] else None,
-                r["dD_part"].sum(dim=0) if need[5] else None,
-                r["dz"].view(batch, L, Di) if zs is not None and need[6] else None)
+        return _input_grads(r, ctx.needs_input_grad, batch, L, Di, N)
+
+
+class _TreeScan(torch.autograd.Function):
+    """out = the reference's tree scan (scan_mode="parallel") with gradients to all seven inputs.
+    Forward: the inference kernel itself (ops.ssm_scan at _tree_mode(), ops.ssm_scan_ungated without
+    z), so out is bitwise the inference value and only the inputs are saved.  Backward:
+    ops.ssm_tree_bwd, which recomputes what it needs; dA and dD are the sums of its
+    per-(utterance, channel) partials.  Enqueued on the current stream, no host sync."""
+
+    @staticmethod
+    def forward(ctx, x, dt, A, B, C, D, z):
+        batch, L, Di, N = _scan_operands(x, dt, A, B, C, D, z)
+        Np = ops.scan_state_dim(N)
+        with torch.no_grad():
+            xs, zs, dts, bc, Ap, A2, Dc, out = _tree_forward(x, dt, A, B, C, D, z, batch, L, Di, N, Np)
+        ctx.save_for_backward(xs, dts, bc, Ap, A2, Dc, *(() if zs is None else (zs,)))
+        ctx.dims = (batch, L, Di, N)
+        return out.view(batch, L, Di)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xs, dts, bc, Ap, A2, Dc, *rest = ctx.saved_tensors
+        zs = rest[0] if rest else None
+        batch, L, Di, N = ctx.dims
+        r = ops.ssm_tree_bwd(xs, zs, dts, bc, Ap, A2, Dc, g.to(torch.float32).reshape(batch * L, Di).contiguous(),
+                             batch, L)
+        return _input_grads(r, ctx.needs_input_grad, batch, L, Di, N)
+
+
+def _tree_forward(x, dt, A, B, C, D, z, batch, L, Di, N, Np):
+    """The tree scan by the inference kernels on (B L, .) rows; returns the packed operands and out."""
+    M = batch * L
+    dts = dt.reshape(M, Di).contiguous()
+    bc, Ap = _pad_states(B, C, A, N, Np)
+    A2 = Ap * torch.tensor(ops.LOG2E, dtype=torch.float32)
+    Dc = D.contiguous()
+    if z is not None:
+        xz = torch.cat([x.reshape(M, Di), z.reshape(M, Di)], 1)
+        xs, zs = xz[:, :Di], xz[:, Di:]
+        out = ops.ssm_scan(xz, dts, bc, A2, Dc, batch, L, _tree_mode())
+    else:
+        xs, zs = x.reshape(M, Di).contiguous(), None
+        out = ops.ssm_scan_ungated(xs, dts, bc, A2, Dc, batch, L, _tree_mode())
+    return xs, zs, dts, bc, Ap, A2, Dc, out
 
 
 _UNIT_GATE = 128.0  # silu(128) == 128 exactly in fp32 (exp(-128) rounds to 0): y * 128 / 128 is y, bitwise
 
 
 def selective_scan(x: torch.Tensor, dt: torch.Tensor, A: torch.Tensor, B: torch.Tensor, C: torch.Tensor,
-                   D: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   D: torch.Tensor, z: Optional[torch.Tensor] = None, *,
+                   scan_mode: ScanMode = "sequential") -> torch.Tensor:
     """The selective scan as a differentiable operator: the reference's SelectiveSSM._sequential_scan
     (ssm.py:134-171) with the D skip, times silu(z) when z is given -- what mamba_ssm's
     selective_scan_fn computes for a state matrix shared across channels.
@@ -156,15 +208,33 @@ def selective_scan(x: torch.Tensor, dt: torch.Tensor, A: torch.Tensor, B: torch.
     instance (e.g. 48) runs zero-padded to the next one and dA, dB, dC are sliced back.  Di must be
     a multiple of 1024 / N' channels (N' the kernel state dim), L <= 8192.
 
-    Batches are full-length.  The scan is causal, so for a padded batch zero the upstream gradient
+    scan_mode "sequential" and "mamba" are that recurrence.  "parallel" is the model's default, the
+    reference's tree scan (_parallel_scan, ssm.py:173-295): with P_e = prod_{r <= e} exp(dt_r A),
+
+        h_t = sum over the set bits k of t of P_{e_S} R_S,   S = [t with bits 0..k cleared, + 2^k),
+
+    R_S the recurrence run over S alone from a zero state (so h_0 = 0); out as above.  Its forward
+    is the inference kernel itself (ops.ssm_scan at the tree mode VASR_SCAN_FMA selects,
+    ops.ssm_scan_ungated without z), bitwise, and only the inputs are kept; its gradients come from
+    vasr_ssm_tree_bwd_f32.  Shapes, padding and limits are the same.
+
+    Batches are full-length.  Either scan is causal, so for a padded batch zero the upstream gradient
     on the padded frames: the gradients of the valid frames and of the parameters are then exact."""
     batch, L, Di, N = _scan_operands(x, dt, A, B, C, D, z)
+    if scan_mode not in _SCAN_MODE_ID:
+        raise ValueError(f"selective_scan: unknown scan_mode {scan_mode!r} ('sequential', 'parallel' or 'mamba')")
     _lib.require_device()
     Np = ops.scan_state_dim(N)
     if Di % ops.scan_bwd_channels(Np):
         raise ValueError(f"selective_scan: Di={Di} must be a multiple of {ops.scan_bwd_channels(Np)} at state dim {N}")
     args = (x, dt, A, B, C, D) + ((z,) if z is not None else ())
-    if torch.is_grad_enabled() and any(t.requires_grad for t in args):
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in args)
+    if _SCAN_MODE_ID[scan_mode] == 0:
+        if needs_grad:
+            return _TreeScan.apply(x, dt, A, B, C, D, z)
+        det = [t.detach() for t in (x, dt, A, B, C, D)] + [None if z is None else z.detach()]
+        return _tree_forward(*det, batch, L, Di, N, Np)[-1].view(batch, L, Di)
+    if needs_grad:
         return _SelectiveScan.apply(x, dt, A, B, C, D, z)
     M = batch * L
     gate = z.reshape(M, Di) if z is not None else torch.full((M, Di), _UNIT_GATE, device=x.device)
@@ -292,23 +362,26 @@ class SelectiveSSM(nn.Module):
         g = self.gated_scan(x.reshape(B * L, -1), B, L)
         return ops.gemm(g, self.out_proj.weight).view(B, L, self.d_model)
 
-    def forward_differentiable(self, x: torch.Tensor) -> torch.Tensor:
+    def forward_differentiable(self, x: torch.Tensor, *, tree_scan: bool = False) -> torch.Tensor:
         """The reference's forward (ssm.py:92-132) for training: the projections, softplus and
         A = -exp(A_log) as torch ops on this module's parameters (torch.autograd differentiates
         them), the scan as selective_scan (HIP forward and backward), then out_proj.  loss.backward()
-        reaches all six parameters and x.  scan_mode "sequential" and "mamba" only: "parallel"
-        reproduces the reference's mis-combined tree, a different function of its inputs whose
-        gradient the recurrence's backward kernel does not compute."""
-        if _SCAN_MODE_ID[self.scan_mode] != 1:
+        reaches all six parameters and x.  By default scan_mode "sequential" and "mamba" only:
+        "parallel" reproduces the reference's mis-combined tree, a different function of its inputs
+        whose gradient the recurrence's backward kernel does not compute.  tree_scan=True
+        differentiates the module's own scan mode, whichever it is: the tree's gradient for
+        "parallel" (selective_scan(scan_mode="parallel")), the recurrence's otherwise."""
+        if _SCAN_MODE_ID[self.scan_mode] != 1 and not tree_scan:
             raise NotImplementedError(
                 f"SelectiveSSM.forward_differentiable: scan_mode={self.scan_mode!r} is the reference's tree scan, "
-                "which is not the recurrence the backward kernel differentiates; use 'sequential' or 'mamba'")
+                "which is not the recurrence the backward kernel differentiates; use 'sequential' or 'mamba', "
+                "or pass tree_scan=True for the tree's own gradient")
         F = torch.nn.functional
         xp, z = F.linear(x, self.in_proj.weight).chunk(2, dim=-1)
         Bm, Cm = F.linear(xp, self.x_proj.weight).chunk(2, dim=-1)
         dt = F.softplus(F.linear(xp, self.dt_proj.weight, self.dt_proj.bias))
         A = -torch.exp(self.A_log)
-        y = selective_scan(xp, dt, A, Bm, Cm, self.D, z)
+        y = selective_scan(xp, dt, A, Bm, Cm, self.D, z, scan_mode=self.scan_mode)
         return F.linear(y, self.out_proj.weight)
 
 
@@ -353,6 +426,16 @@ class SSMBlock(nn.Module):
         x2, xz, xdt = self.head(x, pre_norm)
         g = self.ssm.scan(xz, xdt, B, L)
         return self.tail(g, x2, B, L)
+
+    def forward_differentiable(self, x: torch.Tensor, *, tree_scan: bool = False) -> torch.Tensor:
+        """The reference's _forward_impl (ssm.py:404-427) for training: LayerNorms, the causal
+        depthwise conv, the FFN, the residuals and the dropout modules as torch ops on this module's
+        parameters, around SelectiveSSM.forward_differentiable(tree_scan=...) (the scan's HIP
+        forward and backward).  Dropout follows the module's train() / eval() state."""
+        L = x.size(1)
+        u = self.conv(self.norm1(x).transpose(1, 2))[:, :, :L].transpose(1, 2)
+        x = self.dropout(self.ssm.forward_differentiable(u, tree_scan=tree_scan)) + x
+        return self.ffn(self.norm2(x)) + x
 
     # z-in-tail (VERDICT r04 item 4 / r05 next 3): z = in_proj_z(u) feeds only the gate y * silu(z)
     # (ssm.py:106, :129).  The projection GEMM -- bound by its C stores (DESIGN §3.3) -- then
@@ -474,6 +557,13 @@ class LocalSSMProcessor(nn.Module):
             x = layer(x, pre_norm) if i == 0 else layer(x)
         return ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
 
+    def forward_differentiable(self, x: torch.Tensor, *, tree_scan: bool = False) -> torch.Tensor:
+        """The stack for training: every block's forward_differentiable(tree_scan=...), then the
+        final LayerNorm as a torch op."""
+        for layer in self.layers:
+            x = layer.forward_differentiable(x, tree_scan=tree_scan)
+        return self.norm(x)
+
     def forward_pair(self, x: torch.Tensor, norm2: nn.LayerNorm, pre_norm: Optional[nn.LayerNorm] = None):
         """(forward(x), norm2(forward(x))) with both LayerNorms in one launch (the global context's
         query norm right after this stack's final one, ops.layer_norm_pair): bitwise the same."""
@@ -502,3 +592,10 @@ class GlobalSSM(nn.Module):
         if raw:
             return x
         return ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
+
+    def forward_differentiable(self, x: torch.Tensor) -> torch.Tensor:
+        """The stack for training.  Its scan is always the tree (reference ssm.py:530-537), so its
+        blocks always run forward_differentiable(tree_scan=True); then the final LayerNorm."""
+        for layer in self.layers:
+            x = layer.forward_differentiable(x, tree_scan=True)
+        return self.norm(x)

@@ -6,11 +6,13 @@ CTCLoss here is the loss on the HIP path (vasr_ctc_emissions_f32 + vasr_ctc_loss
 forward only, scoring a known transcript; with differentiable=True it also has a backward pass
 (vasr_ctc_loss_alpha_f32 in the forward, vasr_ctc_occupancy_f32 + vasr_ctc_grad_logits_f32 in the
 backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.CTCLoss.  Of the
-model's own kernels the selective scan's recurrence has a backward pass too (velocity_asr.ssm.selective_scan,
-SelectiveSSM.forward_differentiable: vasr_ssm_scan_save_f32 + vasr_ssm_scan_bwd_f32); the layers around it
-are GEMM, LayerNorm, conv and attention, which torch.autograd differentiates as torch ops.  The rest of
-training (backward passes of the fused GEMM, tail and LayerNorm kernels, the tree scan modes, schedulers,
-Trainer) stays outside this build's scope.
+model's own kernels both selective scans have a backward pass too (velocity_asr.ssm.selective_scan: the
+recurrence of scan_mode "sequential" / "mamba", vasr_ssm_scan_save_f32 + vasr_ssm_scan_bwd_f32, and the default
+"parallel" tree, the inference kernel + vasr_ssm_tree_bwd_f32), and SelectiveSSM, SSMBlock, LocalSSMProcessor and
+GlobalSSM have a forward_differentiable built on them; the layers around the scan are GEMM, LayerNorm, conv and
+attention, which torch.autograd differentiates as torch ops.  The rest of training (a whole-model
+forward_differentiable, backward passes of the fused GEMM, tail and LayerNorm kernels, bf16, schedulers, Trainer)
+stays outside this build's scope.
 """
 
 from __future__ import annotations
