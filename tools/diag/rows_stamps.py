@@ -2,10 +2,14 @@
 -DVASR_ROWS_STAMPS (tools/build_variant_lib.sh rowstamps -DVASR_ROWS_STAMPS; VASR_LIB=<that .so>).
 
 Each wave sums s_memtime cycles per phase of its chunk steps -- the counted vmcnt wait, the block
-barrier, the previous chunk's epilogue (split, bias / softplus, 16 buffer stores issued), the DMA
-issue (loader waves) and the chunk's 72 MFMAs + fragment reads -- and writes the sums once at the
-end.  Printed: per phase the mean over loader and over store-only waves, in cycles and as a share
-of the wave's whole kernel time.  Usage: rows_stamps.py [M ...] (composed head GEMM, K = 192).
+barrier, the previous chunk's epilogue (bias / softplus, buffer stores issued), the DMA issue and
+the chunk's 72 MFMAs + fragment reads -- and writes the sums once at the end.  Printed: per phase
+the mean over the waves of each role, in cycles and as a share of the wave's whole kernel time.
+Roles: the 8-wave kernel's loader and store-only waves (-DVASR_ROWS_ROLES=0), or the
+wave-specialised kernel's compute waves (barrier, MFMA, and under "epilogue" the accumulator's
+hand-off to LDS) and memory waves (wait, barrier, DMA issue, epilogue = store issue; with
+-DVASR_ROWS_DMA_WAVES=2 DMA-only and store-only memory waves).
+Usage: rows_stamps.py [M ...] (composed head GEMM, K = 192; ROWS_N=896 the z-in-tail projection).
 """
 import ctypes
 import os
@@ -43,9 +47,12 @@ for M in Ms:
     assert lib.vasr_diag_rows_stamps(ctypes.c_void_p(0)) == 0
     st = buf.view(-1, 8).cpu()
     st = st[st[:, 5] > 0]
-    for kind, sel in (("loader", st[:, 7] == 1), ("store-only", st[:, 7] == 0)):
+    ROLES = ((1, "loader"), (0, "store-only"), (2, "compute"), (3, "memory"), (4, "mem DMA-only"), (5, "mem store-only"))
+    for kind, sel in ((name, st[:, 7] == code) for code, name in ROLES):
+        if not sel.any():
+            continue
         x = st[sel].double()
         tot = x[:, 5].mean().item()
         parts = ", ".join(f"{n} {x[:, i].mean().item():.0f} ({x[:, i].mean().item() / tot:.0%})" for i, n in enumerate(NAMES))
-        print(f"M={M} {kind:10s} waves {int(sel.sum())}, chunks/wave {x[:, 6].mean().item():.1f}: total {tot:.0f} cyc; "
+        print(f"M={M} {kind:14s} waves {int(sel.sum())}, chunks/wave {x[:, 6].mean().item():.1f}: total {tot:.0f} cyc; "
               f"{parts}; max total {x[:, 5].max().item():.0f}", flush=True)

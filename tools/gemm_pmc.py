@@ -46,7 +46,8 @@ def main():
         # the engine the launcher picks (gemm_rows.hip try_rows_x3: K = 192, N >= 512, M >= 4096,
         # unpaired non-argmax epilogues -> A-rows-stationary; else the LDS-ring tiles)
         rows = K == 192 and N >= 512 and m >= 4096 and epi in ("none", "gelu", "softplus")
-        kernel = "gemm_rows_kernel" if rows else "gemm_x3_kernel"
+        # (gemm_rows_roles_kernel, the wave-specialised form; gemm_rows_kernel in a -DVASR_ROWS_ROLES=0 build)
+        kernel = os.environ.get("ROWS_KERNEL", "gemm_rows_roles_kernel") if rows else "gemm_x3_kernel"
         flops = 2.0 * m * N * K
         if epi == "tailg":
             D, Ei = 192, 384

@@ -1,7 +1,8 @@
 """Composed projection GEMM (u @ [W_in; W_xdt W_in_x]^T, softplus on the dt columns) alone, at the
 bench's launch shapes: rows engine time per launch (HIP events over back-to-back launches) and
 bitwise equality with the tile engine.  Usage (GPU box): python tools/rows_bench.py [M ...]
-(VASR_LIB=<variant .so> selects a diagnostic build)."""
+(VASR_LIB=<variant .so> selects a diagnostic build; ROWS_N=896 times only the z-in-tail projection
+[x | B | C | dt], softplus from column 512, rows engine against tiles)."""
 import os
 import sys
 
@@ -33,6 +34,21 @@ def main():
     lib = os.environ.get("VASR_LIB", "default")
     for M in Ms:
         u = torch.randn(M, 192, device="cuda", generator=g0)
+        if os.environ.get("ROWS_N") == "896":
+            w8 = torch.cat([w[:384], w[768:]]).contiguous()
+            b8 = torch.cat([b[:384], b[768:]]).contiguous()
+            out8 = torch.empty(M, 896, device="cuda")
+
+            def run8():
+                return ops.gemm(u, w8, b8, epilogue=_lib.EPI_SOFTPLUS_FROM, n_out=512, out=out8)
+            res = {}
+            for eng in (2, 1):
+                with ops.option(_lib.OPT_GEMM_ENGINE, eng):
+                    res[eng] = (timed(run8), run8().clone())
+            flops = 6 * 2.0 * M * 896 * 192
+            print(f"lib={os.path.basename(lib)} M={M} N=896: rows {res[2][0]:.2f} us ({flops / res[2][0] / 1e6:.0f} bf16-TF/s), "
+                  f"tiles {res[1][0]:.2f} us, bitwise equal {torch.equal(res[1][1], res[2][1])}", flush=True)
+            continue
         out = torch.empty(M, 1280, device="cuda")
 
         def run():

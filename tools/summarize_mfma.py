@@ -26,7 +26,7 @@ PEAK_BF16 = 2500e12
 PEAK_F32 = 157.3e12
 
 
-FAMILIES = ("gemm_x3_kernel", "gemm_rows_kernel", "ssm_tail_gated_kernel", "ssm_tail_kernel")
+FAMILIES = ("gemm_x3_kernel", "gemm_rows_kernel", "gemm_rows_roles_kernel", "ssm_tail_gated_kernel", "ssm_tail_kernel")
 
 
 def family_rows(path):

@@ -22,6 +22,10 @@
 // chunk's DMA issued before the previous epilogue / no store waits in non-loader waves
 // (profiles/r03r), and the epilogue interleaved into the next chunk's k-steps at 4 or 8 waves
 // (37.0 / 37.6 vs 33.4 us, profiles/r03u).
+//
+// What the launcher runs since round 7 is the wave-specialised form further down
+// (gemm_rows_roles_kernel: compute waves and memory waves, 128-row blocks); the kernel described
+// above is kept for -DVASR_ROWS_ROLES=0 builds (A/B through tools/build_variant_lib.sh).
 #include <type_traits>
 
 #include "gemm_common.h"
@@ -331,17 +335,383 @@ __global__ __launch_bounds__(64 * RW, 1) void gemm_rows_kernel(GemmParams p, int
 #endif
 }
 
-template <int KS>
-int launch_rows(const GemmParams& p, int epi, hipStream_t s) {
+// ---------------------------------------------------------------------------------------------
+// Wave-specialised form (what VASR_OPT_GEMM_ENGINE 2 runs; -DVASR_ROWS_ROLES=0 restores the
+// kernel above).  In the kernel above every wave that owns MFMA work also issues vector memory:
+// a wave issues in order, so while its buffer store or LDS-DMA waits on the backed-up memory
+// pipeline (~190 / ~160 cycles per instruction, profiles/r06r) it issues no MFMA, and the launch
+// takes the sum of its MFMA-only and memory-only ablations (13.5 + 28.4 vs 43.9 us).
+// Here the two kinds of work sit in different waves of the block:
+//   waves 0-3, compute (one per SIMD: waves w and w + 4 share one): 32 rows of A each as three
+//     bf16 planes in VGPRs; per chunk the 72 MFMAs of the kernel above in the same order into
+//     one accumulator, which then goes to a per-wave LDS staging tile (row-major 32 x 32 floats,
+//     16 conflict-free ds_write_b32).  No global load, store or LDS-DMA inside the chunk loop.
+//   waves 4-7, memory: the W chunks' LDS-DMA two chunks ahead, and chunk j - 1's epilogue while
+//     the compute waves multiply chunk j: the staged tile read back as float4 (lane = 4 columns
+//     of one row, 8 lanes per row), rows_epilogue's arithmetic per element, one 16-byte buffer
+//     store per lane and 8 rows (4 store instructions per chunk instead of 16).
+// A block is 128 rows x the chunks of one column group (the VGPR file holds four 256-register
+// compute waves beside four memory waves, not eight), so W streams through LDS once per 128 rows.
+// Group g of G takes chunks g, g + G, ...: every block gets its share of the softplus columns
+// (a contiguous run gave half the blocks all of the exp / log work: 43.3 vs 40.9 us, profiles/r07b).
+// Measured (M = 16032, N = 896, profiles/r07a-c): the memory waves' step, not the
+// MFMAs, still sets the pace; two DMA-only + two store-only memory waves are slower than four that
+// do both (48.2 vs 39.5 us: 18 DMA pieces per wave and step issue one after the other); the epilogue
+// before the step's DMA beats the DMA first (36.2 vs 40.9 us).
+//
+// Hand-off is by workgroup barriers only.  INVARIANT: every wave of a block executes exactly
+// nc + 1 barriers, B_0 .. B_nc, whatever its role, its rows (ragged M: all waves run, addresses
+// clamped, stores dropped) and nc (nc <= 0 returns before any barrier, block-uniform).
+//   compute wave:  for j in [0, nc): { B_j; MFMA chunk j from W slot j % 3; tile j -> stage[j & 1];
+//                  lgkmcnt(0) }   B_nc
+//   memory wave:   DMA(0), DMA(1); for j in [0, nc): { wait DMA(j); B_j; epilogue(j - 1) from
+//                  stage[(j - 1) & 1]; DMA(j + 2) -> slot (j + 2) % 3 }   B_nc; epilogue(nc - 1)
+// What each barrier certifies (checked on paper for nc = 1, 2, 3 and longer odd / even runs):
+//   B_j, W:      DMA(j) has landed (the issuing waves' vmcnt wait precedes B_j), and every
+//                compute wave has consumed chunk j - 1 -- its fragment reads fed the MFMAs whose
+//                result it staged before B_j -- so slot (j - 1) % 3 = (j + 2) % 3 is free.
+//   B_j, tiles:  tile j - 1 is complete in stage[(j - 1) & 1] (lgkmcnt(0) before B_j), and the
+//                memory waves' reads of tile j - 2 from stage[j & 1] have returned (their stores
+//                took the data from registers before B_j), so chunk j's tile may overwrite it.
+//   B_0 also publishes the bias / qparam tables, filled by the memory waves during the A prologue.
+//   nc = 1: B_0, chunk 0, B_1, epilogue(0).  nc = 2: DMA(2) never issues.  nc = 3: DMA(2) is
+//   the only in-loop DMA and fills the slot no chunk has used.
+#ifndef VASR_ROWS_ROLES
+#define VASR_ROWS_ROLES 1
+#endif
+#ifndef VASR_ROWS_INTERLEAVE
+#define VASR_ROWS_INTERLEAVE 1  // column group g of G takes chunks g, g + G, ... (0: a contiguous run), so every block
+#endif                          // gets its share of the softplus columns' exp / log work
+#ifndef VASR_ROWS_EPI_FIRST
+#define VASR_ROWS_EPI_FIRST 1  // a memory wave runs chunk j - 1's epilogue before it issues DMA(j + 2) (0: after): its
+#endif                         // stores are then older than the 9 DMA pieces the next step's vmcnt wait leaves pending
+#ifndef VASR_ROWS_DMA_WAVES
+#define VASR_ROWS_DMA_WAVES 4  // memory waves that issue LDS-DMA: 4 (each also stores) or 2 (two DMA-only, two store-only)
+#endif
+constexpr int CWV = 4;                            // compute waves
+constexpr int MWV = 4;                            // memory waves
+constexpr int DWV = VASR_ROWS_DMA_WAVES;          // the first DWV memory waves issue the DMA
+constexpr int SWV = DWV == MWV ? MWV : MWV - DWV;  // the last SWV memory waves run the epilogues
+static_assert(DWV == 4 || DWV == 2, "VASR_ROWS_DMA_WAVES: 4 or 2");
+constexpr int OOB16 = 0x7FFFFFF0;
+
+// workgroup barrier that the compiler moves no memory access across (the builtin alone is no
+// memory operation to it: an LDS read could be hoisted above the barrier that publishes it)
+__device__ __forceinline__ void role_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// rows_epilogue's per-element arithmetic (same operations, same order)
+template <int EPI, int SP>
+__device__ __forceinline__ float rows_value(const GemmParams& p, float v, float bv, const float4& qc, int row, int col) {
+    if (p.bias) v = v + bv;
+    if (p.qp) v = fake_quant(v, qc);
+    if constexpr (EPI == VASR_EPI_GELU) {
+        v = gelu_fast(v);
+    } else if constexpr (EPI == VASR_EPI_SOFTPLUS_FROM) {
+        if constexpr (SP == 1) v = softplus20_fast(v);
+        else if constexpr (SP == 2) v = col >= p.n_out ? softplus20_fast(v) : v;
+    } else if constexpr (EPI == VASR_EPI_RESIDUAL) {
+        v = v + p.aux[(int64_t)min(row, p.M - 1) * p.ld_aux + min(col, p.N - 1)];
+    } else if constexpr (EPI == VASR_EPI_GELU_PE) {
+        v = gelu_fast(v) + p.aux[(int64_t)min(row, p.M - 1) * p.ld_aux + min(col, p.N - 1)];
+    }
+    return v;
+}
+
+// Epilogue of one staged 32 x 32 tile by one memory wave: lane l owns columns 4 (l & 7) .. + 3 of
+// rows (l >> 3) + 8 s, s = 0..3.  wide (N, ldc multiples of 4 and C 16-byte aligned): one 16-byte
+// store per lane and s; otherwise four dword stores.  Out-of-range lanes store past num_records.
+template <int EPI>
+__device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buffer_rsrc_t cbuf, int m0, int n0,
+                                               const float* __restrict__ tile, int lane, bool wide,
+                                               const float* __restrict__ bias_s, const float4* __restrict__ qp_s,
+                                               int cfirst) {
+    const int rl = lane >> 3, c4 = 4 * (lane & 7);
+    const int col0 = n0 + c4;
+    const int lc = col0 - cfirst;  // column in the group's LDS tables
+    float bv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (p.bias) {
+        const float4 b = *reinterpret_cast<const float4*>(bias_s + lc);
+        bv[0] = b.x; bv[1] = b.y; bv[2] = b.z; bv[3] = b.w;
+    }
+    float4 qc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) qc[e] = p.qp ? qp_s[lc + e] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (EPI == VASR_EPI_ARGMAX) {
+        const int slot = n0 / 32;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int row = m0 + 8 * s + rl;
+            const float4 x = *reinterpret_cast<const float4*>(tile + (8 * s + rl) * 32 + c4);
+            const float xv[4] = {x.x, x.y, x.z, x.w};
+            unsigned long long key = 0ull;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = xv[e];
+                if (p.bias) v = v + bv[e];
+                if (p.qp) v = fake_quant(v, qc[e]);
+                const unsigned u = __float_as_uint(v);
+                const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+                const unsigned long long k =
+                    col0 + e < p.N ? ((unsigned long long)ord << 32) | (0xFFFFFFFFu - (unsigned)(col0 + e)) : 0ull;
+                key = k > key ? k : key;
+            }
+            // the row's 8 lanes: xor 1, xor 2 within the quad, then the mirrored other quad
+            unsigned long long o = gemm::dpp_u64<0xB1, 0xF>(key);
+            key = o > key ? o : key;
+            o = gemm::dpp_u64<0x4E, 0xF>(key);
+            key = o > key ? o : key;
+            o = gemm::dpp_u64<0x141, 0xF>(key);
+            key = o > key ? o : key;
+            const int off = (c4 == 0 && row < p.M) ? (row * (int)p.ldc + slot) * 8 : OOB16;
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            const u32x2 kv = {(unsigned)key, (unsigned)(key >> 32)};
+            __builtin_amdgcn_raw_buffer_store_b64(kv, cbuf, off, 0, VASR_ROWS_STORE_AUX);
+        }
+        return;
+    }
+    auto body = [&](auto SPc, auto Wc) {
+        constexpr int SP = decltype(SPc)::value;
+        constexpr bool WIDE = decltype(Wc)::value;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int row = m0 + 8 * s + rl;
+            const float4 x = *reinterpret_cast<const float4*>(tile + (8 * s + rl) * 32 + c4);
+            float v[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rows_value<EPI, SP>(p, v[e], bv[e], qc[e], row, col0 + e);
+            if constexpr (WIDE) {
+                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4 d = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+                const int off = (row < p.M && col0 < p.N) ? (row * (int)p.ldc + col0) * 4 : OOB16;
+                if (!(VASR_ROWS_ABLATE & 2) || s == 3) __builtin_amdgcn_raw_buffer_store_b128(d, cbuf, off, 0, VASR_ROWS_STORE_AUX);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e]), cbuf,
+                                                          (row < p.M && col0 + e < p.N) ? (row * (int)p.ldc + col0 + e) * 4 : OOB,
+                                                          0, VASR_ROWS_STORE_AUX);
+            }
+        }
+    };
+    auto width = [&](auto SPc) {
+        if (wide) body(SPc, std::true_type());
+        else body(SPc, std::false_type());
+    };
+    // whole chunks branch on the softplus columns, as rows_epilogue does (n0 is wave-uniform)
+    if constexpr (EPI == VASR_EPI_SOFTPLUS_FROM) {
+        if (n0 >= p.n_out) width(std::integral_constant<int, 1>());
+        else if (n0 + 32 <= p.n_out) width(std::integral_constant<int, 0>());
+        else width(std::integral_constant<int, 2>());
+    } else {
+        width(std::integral_constant<int, 0>());
+    }
+}
+
+template <int KS, int EPI>
+__global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(GemmParams p, int n_groups,
+                                                                              int chunks_per_group, int wide) {
+    constexpr int CHUNK = KS * 3 * 1024;   // one 32-column W chunk: [KS][3 planes][64 lanes][16 B]
+    constexpr int NDMA = 3 * KS / DWV;     // LDS-DMA instructions per DMA wave per chunk
+    static_assert((3 * KS) % DWV == 0, "whole DMA pieces per DMA wave");
+    static_assert(DEPTH == 2, "the roles kernel's ring is three slots, two chunks ahead");
+    __shared__ __attribute__((aligned(16))) char wb0[CHUNK];
+    __shared__ __attribute__((aligned(16))) char wb1[CHUNK];
+    __shared__ __attribute__((aligned(16))) char wb2[CHUNK];
+    __shared__ __attribute__((aligned(16))) float stage[CWV][2][1024];  // per compute wave, two 32 x 32 tiles
+    __shared__ __attribute__((aligned(16))) float bias_s[MAX_GROUP * 32];
+    __shared__ float4 qp_s[MAX_GROUP * 32];
+
+    const int nblk = (int)gridDim.x;
+    const int id = blockIdx.x;
+    const int q8 = nblk / 8, r8 = nblk % 8, xg = id % 8;
+    const int w = (xg < r8 ? xg * (q8 + 1) : r8 * (q8 + 1) + (xg - r8) * q8) + id / 8;
+    const int rb = w / n_groups, ng = w - rb * n_groups;
     const int NT = (p.N + 31) / 32;
-    const int row_blocks = (p.M + 32 * RW - 1) / (32 * RW);
-    // column groups: at most one block per CU (LDS: NSLOT x 36 KiB per block), so a grid of more
-    // than kCUs blocks runs in rounds, and a partial round costs as much as a full one.  The
-    // groups minimise rounds x (chunks per block + 1), the 1 standing for a block's A prologue
-    // (its 256 rows loaded and split): M = 16032 keeps 4 groups of 10 chunks (252 blocks, one
-    // round); the 30-s clips' M = 48096 takes 4 groups in 3 rounds (30 chunk-steps per CU) instead
-    // of 3 groups of 16 (the MAX_GROUP cap) in 3 rounds (48), M = 24048 5 groups of 8 in 2 rounds
-    // (16) instead of 3 of 16 in 2 (32).
+    // chunk j of this block: group ng's j-th chunk
+    constexpr bool IL = VASR_ROWS_INTERLEAVE != 0;
+    const int c0 = IL ? ng : ng * chunks_per_group, cstep = IL ? n_groups : 1;
+    const int nc = IL ? (NT - ng + n_groups - 1) / n_groups : min(chunks_per_group, NT - c0);
+    if (nc <= 0) return;  // block-uniform, before any barrier
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    auto slot = [&](int i) -> char* { return i == 0 ? wb0 : i == 1 ? wb1 : wb2; };
+#ifdef VASR_ROWS_STAMPS
+    unsigned long long st_wait = 0, st_bar = 0, st_epi = 0, st_dma = 0, st_mfma = 0;
+    VASR_STAMP(st_begin);
+#endif
+
+    if (wave_u < CWV) {
+        // ---- compute wave ----
+        const int r = lane & 31, h = lane >> 5;
+        const int m0 = rb * 32 * CWV + wave_u * 32;
+        const float* __restrict__ arow = p.A + (int64_t)min(m0 + r, p.M - 1) * p.lda;
+        float4 xa[KS][2];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int k = 16 * ks + 8 * h + 4 * u;
+                const float4 v = *reinterpret_cast<const float4*>(arow + min(k, p.K - 4));
+                xa[ks][u] = k < p.K ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        bf16x8 a[KS][3];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) split8(xa[ks][0], xa[ks][1], a[ks][0], a[ks][1], a[ks][2]);
+        for (int j = 0; j < nc; ++j) {
+            VASR_STAMP(t0);
+            role_barrier();  // B_j
+            VASR_STAMP(t1);
+            const char* wb = slot(j % NSLOT) + lane * 16;
+            bf16x8 wf[2][3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) wf[0][pl] = *reinterpret_cast<const bf16x8*>(wb + pl * 1024);
+            floatx16 c;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) c[i] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int cur = ks & 1;
+                if (ks + 1 < KS) {  // next k-step's fragments one step ahead of their MFMAs
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl)
+                        wf[cur ^ 1][pl] = *reinterpret_cast<const bf16x8*>(wb + ((ks + 1) * 3 + pl) * 1024);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // small terms first, then the leading hi*hi term (gemm_x3.hip's order)
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][2], wf[cur][0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][0], wf[cur][2], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][1], wf[cur][1], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][1], wf[cur][0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][0], wf[cur][1], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][0], wf[cur][0], c, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            VASR_STAMP(t2);
+            // element i of lane (r, h) is row (i & 3) + 8 (i >> 2) + 4 h, column r: lanes 0-31 and
+            // 32-63 each write one 128-byte row per instruction
+            float* tile = &stage[wave_u][j & 1][0];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) tile[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = c[i];
+            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the tile is in LDS before B_{j+1}
+#ifdef VASR_ROWS_STAMPS
+            VASR_STAMP(t3);
+            st_bar += t1 - t0;
+            st_mfma += t2 - t1;
+            st_epi += t3 - t2;  // compute waves: the tile's hand-off to LDS
+#endif
+        }
+        VASR_STAMP(t4);
+        role_barrier();  // B_nc
+#ifdef VASR_ROWS_STAMPS
+        VASR_STAMP(t5);
+        st_bar += t5 - t4;
+#endif
+    } else {
+        // ---- memory wave ----
+        const int mw = wave_u - CWV;
+        const bool dma = mw < DWV;
+        const bool stores = mw >= MWV - SWV;
+        const int sw = mw - (MWV - SWV);  // index among the storing waves
+        for (int i = tid - 64 * CWV; i < nc * 32; i += 64 * MWV) {  // tables: 32 entries per chunk of the block
+            const int col = min((c0 + (i >> 5) * cstep) * 32 + (i & 31), p.N - 1);
+            if (p.bias) bias_s[i] = p.bias[col];
+            if (p.qp) qp_s[i] = p.qp[col];
+        }
+        const char* __restrict__ Wx = reinterpret_cast<const char*>(p.Wx);
+        auto issue = [&](int j) {
+            const char* src = Wx + (int64_t)(c0 + j * cstep) * CHUNK + lane * 16;
+            char* dst = slot(j % NSLOT);
+#pragma unroll
+            for (int i = 0; i < NDMA; ++i) {
+                const int piece = i * DWV + mw;
+                glds16(src + piece * 1024, dst + piece * 1024);
+            }
+        };
+        // the table fills above are plain loads: the compiler has waited for them before their LDS
+        // writes, so the DMA pieces below are this wave's only outstanding loads from here on
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the tables are in LDS before B_0
+        if (dma)
+            for (int j = 0; j < DEPTH && j < nc; ++j) issue(j);
+        const int c_bytes = (EPI == VASR_EPI_ARGMAX ? 8 : 4) * ((p.M - 1) * (int)p.ldc + (EPI == VASR_EPI_ARGMAX ? NT : p.N));
+        const __amdgpu_buffer_rsrc_t cbuf = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, c_bytes, 0x00020000);
+        auto epilogue = [&](int j) {  // chunk j's tiles of compute waves sw, sw + SWV, ...
+            if (!stores) return;
+            const int n0 = (c0 + j * cstep) * 32;
+            for (int cw = sw; cw < CWV; cw += SWV)
+                roles_epilogue<EPI>(p, cbuf, rb * 32 * CWV + cw * 32, n0, &stage[cw][j & 1][0], lane, wide != 0,
+                                    bias_s, qp_s, n0 - j * 32);
+        };
+        for (int j = 0; j < nc; ++j) {
+            VASR_STAMP(t0);
+            // DMA(j) must have landed before B_j.  vmcnt counts this wave's loads and stores
+            // together, and a store may retire before an older load, so a count that allowed for
+            // younger stores would prove nothing (profiles/r04b).  Loads retire in order among
+            // themselves, and the only loads younger than DMA(j) are DMA(j + 1)'s NDMA pieces, if
+            // that chunk exists: with at most that many operations of any kind outstanding, a
+            // pending piece of DMA(j) would need all NDMA younger loads pending beside it, one more
+            // than the count allows.  (For a wave that also stores this bounds its stores in flight
+            // to the same NDMA; a store-only wave never waits: the staging tiles are recycled on
+            // their LDS reads, not on the stores' completion.)
+            if (dma) {
+                if (j + 1 < nc) wait_vmcnt<NDMA*(DEPTH - 1)>();
+                else wait_vmcnt<0>();
+            }
+            VASR_STAMP(t1);
+            role_barrier();  // B_j
+            VASR_STAMP(t2);
+            if (VASR_ROWS_EPI_FIRST && j >= 1) epilogue(j - 1);
+            VASR_STAMP(t2e);
+            if (dma && j + DEPTH < nc && !(VASR_ROWS_ABLATE & 4)) issue(j + DEPTH);
+            VASR_STAMP(t3);
+            if (!VASR_ROWS_EPI_FIRST && j >= 1) epilogue(j - 1);
+#ifdef VASR_ROWS_STAMPS
+            VASR_STAMP(t4);
+            st_wait += t1 - t0;
+            st_bar += t2 - t1;
+            st_dma += t3 - t2e;
+            st_epi += (t2e - t2) + (t4 - t3);
+#endif
+        }
+        VASR_STAMP(t5);
+        role_barrier();  // B_nc
+        VASR_STAMP(t6);
+        epilogue(nc - 1);
+#ifdef VASR_ROWS_STAMPS
+        VASR_STAMP(t7);
+        st_bar += t6 - t5;
+        st_epi += t7 - t6;
+#endif
+    }
+#ifdef VASR_ROWS_STAMPS
+    __builtin_amdgcn_s_waitcnt(0);
+    VASR_STAMP(st_end);
+    if (lane == 0 && g_rows_stamps) {
+        unsigned long long* o = g_rows_stamps + ((int64_t)blockIdx.x * (CWV + MWV) + wave_u) * 8;
+        o[0] = st_wait; o[1] = st_bar; o[2] = st_epi; o[3] = st_dma; o[4] = st_mfma; o[5] = st_end - st_begin;
+        o[6] = (unsigned long long)nc;
+        // role: 2 compute, 3 memory (DMA and stores), 4 DMA-only, 5 store-only (0 / 1: the kernel above)
+        o[7] = wave_u < CWV ? 2 : DWV == MWV ? 3 : wave_u - CWV < DWV ? 4 : 5;
+    }
+#endif
+}
+
+// Column groups (runs of chunks) for row_blocks blocks of rows: at most one block per CU (LDS), so
+// a grid of more than kCUs blocks runs in rounds, and a partial round costs as much as a full one.
+// The groups minimise rounds x (chunks per block + 1), the 1 standing for a block's A prologue (its
+// rows loaded and split; a wave's 32 rows in either form).  256-row blocks: M = 16032 keeps 4 groups
+// of 10 chunks at N = 1280 (252 blocks, one round); the 30-s clips' M = 48096 takes 4 groups in 3
+// rounds (30 chunk-steps per CU) instead of 3 groups of 16 (the MAX_GROUP cap) in 3 rounds (48),
+// M = 24048 5 groups of 8 in 2 rounds (16) instead of 3 of 16 in 2 (32).  128-row blocks (the roles
+// kernel), N = 896 (28 chunks): M = 16032 is 126 row blocks x 2 groups of 14 = 252 blocks in one
+// round (cost 15; 3 groups of 10 would be 378 blocks, 2 rounds, 22), M = 8016 63 x 4 groups of 7 (8),
+// M = 48096 376 x 2 of 14 = 752 blocks, 3 rounds (45; 4 groups of 7: 6 rounds, 48).
+inline void pick_groups(int row_blocks, int NT, int* groups_out, int* per_out) {
     int groups = 1, per = min(NT, MAX_GROUP), best = -1;
     for (int g = 1; g <= NT; ++g) {
         const int pg = (NT + g - 1) / g;
@@ -354,6 +724,39 @@ int launch_rows(const GemmParams& p, int epi, hipStream_t s) {
             per = pg;
         }
     }
+    *groups_out = groups;
+    *per_out = per;
+}
+
+template <int KS>
+int launch_roles(const GemmParams& p, int epi, hipStream_t s) {
+    const int NT = (p.N + 31) / 32;
+    const int row_blocks = (p.M + 32 * CWV - 1) / (32 * CWV);
+    int groups, per;
+    pick_groups(row_blocks, NT, &groups, &per);
+    // 16-byte stores need every lane's 4 columns valid together and 16-byte aligned
+    const int wide = epi != VASR_EPI_ARGMAX && p.N % 4 == 0 && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
+    const dim3 grid(row_blocks * groups), block(64 * (CWV + MWV));
+#define VASR_R(E) hipLaunchKernelGGL((gemm_rows_roles_kernel<KS, E>), grid, block, 0, s, p, groups, per, wide)
+    switch (epi) {
+        case VASR_EPI_NONE: VASR_R(VASR_EPI_NONE); break;
+        case VASR_EPI_GELU: VASR_R(VASR_EPI_GELU); break;
+        case VASR_EPI_SOFTPLUS_FROM: VASR_R(VASR_EPI_SOFTPLUS_FROM); break;
+        case VASR_EPI_RESIDUAL: VASR_R(VASR_EPI_RESIDUAL); break;
+        case VASR_EPI_GELU_PE: VASR_R(VASR_EPI_GELU_PE); break;
+        case VASR_EPI_ARGMAX: VASR_R(VASR_EPI_ARGMAX); break;
+        default: set_error("vasr_linear_x3_f32: rows engine: epilogue %d not supported", epi); return VASR_EINVAL;
+    }
+#undef VASR_R
+    return launch_status("vasr_linear_x3_f32");
+}
+
+template <int KS>
+int launch_rows(const GemmParams& p, int epi, hipStream_t s) {
+    const int NT = (p.N + 31) / 32;
+    const int row_blocks = (p.M + 32 * RW - 1) / (32 * RW);
+    int groups, per;
+    pick_groups(row_blocks, NT, &groups, &per);
     const dim3 grid(row_blocks * groups), block(64 * RW);
 #define VASR_R(E) hipLaunchKernelGGL((gemm_rows_kernel<KS, E>), grid, block, 0, s, p, groups, per)
     switch (epi) {
@@ -388,7 +791,13 @@ bool try_rows_x3(const GemmParams& p, int batch, int epi, hipStream_t s, int* rc
     if (engine == 0 && (p.Kp != 192 || p.N < 512 || p.M < 4096 ||
                         !(epi == VASR_EPI_NONE || epi == VASR_EPI_GELU || epi == VASR_EPI_SOFTPLUS_FROM)))
         return false;
-    *rc = p.Kp == 128 ? launch_rows<8>(p, epi, s) : launch_rows<12>(p, epi, s);
+    // the wave-specialised kernel: whatever engine 2 is forced on, and every shape auto sends here (it
+    // measured faster than the 8-wave kernel at each of them, interleaved, profiles/r07c/gemm_ab.txt: N = 896 at
+    // M = 8016 20.6 vs 29.7 us, 16032 34.8 vs 45.9, 24016 58.6 vs 74.1, 48096 104.3 vs 129.6; N = 1280 at
+    // M = 16032 50.5 vs 60.2); -DVASR_ROWS_ROLES=0 builds a library that runs the 8-wave kernel instead
+    const bool roles = VASR_ROWS_ROLES != 0;
+    if (roles) *rc = p.Kp == 128 ? launch_roles<8>(p, epi, s) : launch_roles<12>(p, epi, s);
+    else *rc = p.Kp == 128 ? launch_rows<8>(p, epi, s) : launch_rows<12>(p, epi, s);
     return true;
 }
 
