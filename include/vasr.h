@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define VASR_ABI_VERSION 20
+#define VASR_ABI_VERSION 21
 
 #define VASR_OK 0
 #define VASR_EINVAL (-1)
@@ -138,6 +138,14 @@ int64_t vasr_split_weights_elems(int N, int K);
 int vasr_linear_bf16(const vasr_gemm_args* args, const uint16_t* w_packed, void* stream);
 int vasr_pack_weights_bf16(const uint16_t* W, int64_t ldw, int N, int K, uint16_t* out, void* stream);
 int64_t vasr_pack_weights_bf16_elems(int N, int K);
+
+/* Which kernel the matching vasr_linear_x3_f32 (bf16 = 0) or vasr_linear_bf16 (bf16 = 1) call
+ * would launch under the current options, for a dense C (ABI 21).  Host only, launches nothing;
+ * the launchers take their decision from the same rule.  Returns 128128, 128064 or 64064 for the
+ * 128 x 128, 128 x 64 and 64 x 64 tile kernels, 1 for the A-rows-stationary engine
+ * (VASR_OPT_GEMM_ENGINE), VASR_EINVAL for M, N, K or batch < 1 (a call with M = 0 launches
+ * nothing), K % 4 != 0, an unknown epilogue, a paired epilogue with N % 64 != 0, bf16 not 0 / 1. */
+int vasr_gemm_tile(int M, int N, int K, int batch, int epilogue, int bf16);
 
 /* ------------------------------------------------------------------ norms / conv
  * nn.LayerNorm over the last dim (C <= 1024), biased variance.  y may alias x.

@@ -29,7 +29,7 @@ def test_new_symbols_are_declared_exported_and_bound_under_abi_20(lib):
     import velocity_asr as v
     from velocity_asr import _lib, ops
 
-    assert _lib.ABI_VERSION == 20 and lib.vasr_version() == 20
+    assert _lib.ABI_VERSION == 21 and lib.vasr_version() == 21
     for name in NEW:
         assert name in _lib.header_functions() and name in _lib._SIGNATURES and hasattr(lib, name)
     for name in ("ctc_loss_alpha", "ctc_occupancy", "ctc_grad_logits"):

@@ -37,7 +37,7 @@ def test_new_names_import_and_public_all_is_unchanged():
 
 def test_abi_version_20_and_bindings(lib):
     from velocity_asr import _lib
-    assert _lib.ABI_VERSION == 20 and lib.vasr_version() == 20
+    assert _lib.ABI_VERSION == 21 and lib.vasr_version() == 21
     for name in ("vasr_ctc_emissions_f32", "vasr_ctc_loss_f32", "vasr_ctc_align_f32",
                  "vasr_ctc_align_workspace_bytes"):
         assert name in _lib.header_functions() and name in _lib._SIGNATURES

@@ -234,6 +234,58 @@ def test_scan_form_follows_the_library_rule():
         assert sel(1, 501, 384, 64) == 0
 
 
+def test_gemm_tile_query_pins_the_dispatch_rule():
+    """vasr_gemm_tile (ABI 21) is the launchers' own rule (gemm_x3.hip select_kernel): pinned at the
+    picker's edges (128 x 128 from 486 tiles, 128 x 64 from 358) and at the model's shapes, so a retune
+    shows up here and in tests/test_gemm_tiles.py, whose cases assert the tile they run on."""
+    from velocity_asr import _lib, ops
+    lib = _lib.load()
+    T128, T12864, T64, ROWS = 128128, 128064, 64064, 1
+    K = 384  # not 128 / 192: off the rows engine
+    for bf16 in (False, True):
+        assert ops.gemm_tile(7680, 1024, K, bf16=bf16) == T12864  # 480 tiles of 128 x 128: below 486
+        assert ops.gemm_tile(7681, 1024, K, bf16=bf16) == T128  # 488
+        for M in (1, 300, 16032, 1 << 20):  # N <= 192: 64 x 64 at any M
+            assert ops.gemm_tile(M, 192, K, bf16=bf16) == T64
+        assert ops.gemm_tile(9217, 320, K, bf16=bf16) == T12864  # N % 128 != 0 and N <= 512; 365 tiles
+        assert ops.gemm_tile(9089, 320, K, bf16=bf16) == T12864  # 360 tiles
+        assert ops.gemm_tile(9088, 320, K, bf16=bf16) == T64  # 355 tiles of 128 x 64: below 358
+        assert ops.gemm_tile(12417, 640, K, bf16=bf16) == T128
+        assert ops.gemm_tile(1001, 448, 400, batch=32, epilogue=_lib.EPI_PAIR_POWER, bf16=bf16) == T12864
+        for epi in (_lib.EPI_PAIR_POWER, _lib.EPI_PAIR_FUSION):  # pairs never take 64 x 64
+            assert ops.gemm_tile(300, 448, K, epilogue=epi, bf16=bf16) == T12864
+            assert ops.gemm_tile(1, 64, K, epilogue=epi, bf16=bf16) == T12864
+        assert ops.gemm_tile(300, 448, K, bf16=bf16) == T64
+        # the bf16 GEMM has no rows engine: the CTC head's argmax at K = 192 stays on the tiles
+        for engine in (0, 1, 2):
+            with ops.option(_lib.OPT_GEMM_ENGINE, engine):
+                assert ops.gemm_tile(16032, 1000, 192, epilogue=_lib.EPI_ARGMAX, bf16=True) == T128
+                assert ops.gemm_tile(16032, 896, 192, bf16=True) == T128
+    # fp32 at K = 192: engine 0 (auto) / 1 (tiles) / 2 (rows)
+    for engine, want in ((0, ROWS), (1, T128), (2, ROWS)):
+        with ops.option(_lib.OPT_GEMM_ENGINE, engine):
+            assert ops.gemm_tile(16032, 896, 192) == want
+    # auto keeps the tiles for N < 512, M < 4096, the argmax / residual epilogues, batches, other K
+    assert ops.gemm_tile(16032, 384, 192) == T12864 and ops.gemm_tile(4095, 896, 192) == T12864
+    assert ops.gemm_tile(16032, 1000, 192, epilogue=_lib.EPI_ARGMAX) == T128
+    assert ops.gemm_tile(16032, 896, 192, epilogue=_lib.EPI_RESIDUAL) == T128
+    assert ops.gemm_tile(8016, 896, 192, batch=2) == T128 and ops.gemm_tile(16032, 896, 164) == ROWS
+    assert ops.gemm_tile(16032, 896, 224) == T128 and ops.gemm_tile(16032, 896, 128) == T128
+    assert ops.gemm_tile(16032, 896, 160) == T128  # Kp = 160
+    assert ops.gemm_tile(1 << 20, 896, 192) == T128  # C past the rows engine's 31-bit offsets
+    with ops.option(_lib.OPT_GEMM_ENGINE, 2):  # forced: K = 128 too, never pairs or batches
+        assert ops.gemm_tile(33, 64, 128) == ROWS and ops.gemm_tile(33, 64, 100) == ROWS
+        assert ops.gemm_tile(33, 64, 96) == T64 and ops.gemm_tile(33, 64, 128, batch=2) == T64
+        assert ops.gemm_tile(300, 448, 192, epilogue=_lib.EPI_PAIR_FUSION) == T12864
+    # bad arguments: refused as the launchers refuse them, nothing launched
+    for bad in ((0, 64, 32, 1, 0, 0), (4, 0, 32, 1, 0, 0), (4, 64, 34, 1, 0, 0), (4, 64, 32, 0, 0, 0),
+                (4, 64, 32, 1, 8, 0), (4, 64, 32, 1, -1, 0), (4, 64, 32, 1, 0, 2), (4, 96, 32, 1, _lib.EPI_PAIR_POWER, 0)):
+        assert lib.vasr_gemm_tile(*bad) == -1, bad
+    assert b"vasr_gemm_tile" in lib.vasr_last_error()
+    with pytest.raises(RuntimeError, match="vasr_gemm_tile"):
+        ops.gemm_tile(4, 64, 34)
+
+
 def _isa_scan():
     sys.path.insert(0, os.path.join(REPO, "tools", "isa"))
     import isa_scan

@@ -43,7 +43,7 @@ def main():
     order = []
     for name, N, K, epi, lda in (HEAD if which == "head" else SPLIT):
         m = 1024 if epi == "tail1024" else M
-        # the engine the launcher picks (gemm_rows.hip try_rows_x3: K = 192, N >= 512, M >= 4096,
+        # the engine the launcher picks (gemm_rows.hip rows_x3_selected: K = 192, N >= 512, M >= 4096,
         # unpaired non-argmax epilogues -> A-rows-stationary; else the LDS-ring tiles)
         rows = K == 192 and N >= 512 and m >= 4096 and epi in ("none", "gelu", "softplus")
         # (gemm_rows_roles_kernel, the wave-specialised form; gemm_rows_kernel in a -DVASR_ROWS_ROLES=0 build)

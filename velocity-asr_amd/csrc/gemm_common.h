@@ -116,7 +116,7 @@ __device__ __forceinline__ void epilogue_body(const GemmParams& p, const Tile& t
                 if (p.qp) {
                     qg = p.qp[pc];
                     qgl = p.qp[pc + 32];
-                    ql = p.qp[2 * p.n_out + col];
+                    ql = p.qp[p.N + col];  // after the N paired entries, also when n_out < N / 2
                 }
             }
 #pragma unroll
@@ -318,9 +318,10 @@ inline int check_args(const vasr_gemm_args* a, const char* fn, GemmParams& p) {
 
 }  // namespace gemm
 
-// gemm_rows.hip: launches the A-rows-stationary split GEMM when the shape suits it (batch 1,
-// K = 128 / 192, unpaired epilogue) and the engine option allows; returns true with the launch
-// status in *rc, false when the tile kernel should run.
-bool try_rows_x3(const gemm::GemmParams& p, int batch, int epi, hipStream_t s, int* rc);
+// gemm_rows.hip: the A-rows-stationary split GEMM.  rows_x3_selected says whether a launch goes to
+// it (batch 1, K = 128 / 192, unpaired epilogue, and the engine option allows) rather than to the
+// tile kernel; launch_rows_x3 launches it and returns the launch status.
+bool rows_x3_selected(int M, int N, int Kp, int64_t ldc, int batch, int epi);
+int launch_rows_x3(const gemm::GemmParams& p, int epi, hipStream_t s);
 
 }  // namespace vasr

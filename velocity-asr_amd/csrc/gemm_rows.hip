@@ -775,12 +775,13 @@ int launch_rows(const GemmParams& p, int epi, hipStream_t s) {
 }  // namespace
 
 // The rows engine serves batch-1 launches with K <= 192 and unpaired epilogues (the model's
-// projection GEMMs at K = 192, the CTC head); returns false when the tile kernel should run.
-bool try_rows_x3(const GemmParams& p, int batch, int epi, hipStream_t s, int* rc) {
-    if (batch != 1 || p.Kp > 192 || p.M <= 0 || epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION) return false;
-    if (p.Kp != 128 && p.Kp != 192) return false;  // the W chunk stride is Kp / 16 k-steps
+// projection GEMMs at K = 192, the CTC head).  rows_x3_selected is the rule alone (host only, launches
+// nothing: vasr_linear_x3_f32 and vasr_gemm_tile both ask it); false when the tile kernel should run.
+bool rows_x3_selected(int M, int N, int Kp, int64_t ldc, int batch, int epi) {
+    if (batch != 1 || Kp > 192 || M <= 0 || epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION) return false;
+    if (Kp != 128 && Kp != 192) return false;  // the W chunk stride is Kp / 16 k-steps
     // raw-buffer C addressing: the valid bytes must fit the 31-bit offsets
-    if ((int64_t)p.M * p.ldc * (epi == VASR_EPI_ARGMAX ? 8 : 4) >= ((int64_t)1 << 31) - 64) return false;
+    if ((int64_t)M * ldc * (epi == VASR_EPI_ARGMAX ? 8 : 4) >= ((int64_t)1 << 31) - 64) return false;
     const int engine = option(VASR_OPT_GEMM_ENGINE);  // 0 auto, 1 tiles, 2 rows
     if (engine == 1) return false;
     // auto: the rows engine where it measured faster (profiles/r03l: K = 192, N >= 512 -- the
@@ -788,17 +789,21 @@ bool try_rows_x3(const GemmParams& p, int batch, int epi, hipStream_t s, int* rc
     // chunk run does not amortise its A load; one utterance, M = 501: 13.2 vs 8.4 us in the
     // graph, profiles/r03m -- two 256-row blocks per column group); the argmax head keeps the tiles (its per-chunk
     // 32-lane reductions), and so do the residual / GELU+PE epilogues (they spill at 8 waves)
-    if (engine == 0 && (p.Kp != 192 || p.N < 512 || p.M < 4096 ||
+    if (engine == 0 && (Kp != 192 || N < 512 || M < 4096 ||
                         !(epi == VASR_EPI_NONE || epi == VASR_EPI_GELU || epi == VASR_EPI_SOFTPLUS_FROM)))
         return false;
+    return true;
+}
+
+// Launches the rows engine for a call rows_x3_selected accepted.
+int launch_rows_x3(const GemmParams& p, int epi, hipStream_t s) {
     // the wave-specialised kernel: whatever engine 2 is forced on, and every shape auto sends here (it
     // measured faster than the 8-wave kernel at each of them, interleaved, profiles/r07c/gemm_ab.txt: N = 896 at
     // M = 8016 20.6 vs 29.7 us, 16032 34.8 vs 45.9, 24016 58.6 vs 74.1, 48096 104.3 vs 129.6; N = 1280 at
     // M = 16032 50.5 vs 60.2); -DVASR_ROWS_ROLES=0 builds a library that runs the 8-wave kernel instead
     const bool roles = VASR_ROWS_ROLES != 0;
-    if (roles) *rc = p.Kp == 128 ? launch_roles<8>(p, epi, s) : launch_roles<12>(p, epi, s);
-    else *rc = p.Kp == 128 ? launch_rows<8>(p, epi, s) : launch_rows<12>(p, epi, s);
-    return true;
+    if (roles) return p.Kp == 128 ? launch_roles<8>(p, epi, s) : launch_roles<12>(p, epi, s);
+    return p.Kp == 128 ? launch_rows<8>(p, epi, s) : launch_rows<12>(p, epi, s);
 }
 
 }  // namespace vasr

@@ -410,6 +410,25 @@ int pick_x3(int M, int N, int batch, bool pair) {
     return pair ? 1 : 2;  // paired epilogues need an even TN
 }
 
+// The one dispatch rule: what vasr_linear_x3_f32 (bf16 = false) or vasr_linear_bf16 launches for a
+// shape under the current options.  kRows = the rows engine, else an index into kCfgs.  Both
+// launchers and vasr_gemm_tile call it, so the query cannot drift from the launch.
+constexpr int kRows = -1;
+int select_kernel(int M, int N, int K, int64_t ldc, int batch, int epi, bool bf16) {
+    const bool pair = epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION;
+    if (bf16) {
+#ifdef VASR_BF16_FORCE_CFG
+        return VASR_BF16_FORCE_CFG;  // diagnostic builds only
+#endif
+    } else {
+        if (rows_x3_selected(M, N, (K + 31) / 32 * 32, ldc, batch, epi)) return kRows;
+#ifdef VASR_X3_FORCE_CFG
+        return VASR_X3_FORCE_CFG;  // diagnostic builds only
+#endif
+    }
+    return pick_x3(M, N, batch, pair);
+}
+
 // Fragment-native planes [NT][KS][3][64][8] (NT = ceil(N/32), KS = Kp/16): element (n, k)
 // sits in tile n/32, k-step k/16, lane 32*((k%16)/8) + n%32, slot k%8.  One thread per 8
 // consecutive k of one (padded) row; rows >= N and k >= K are zero.
@@ -487,16 +506,9 @@ VASR_API int vasr_linear_x3_f32(const vasr_gemm_args* a, const uint16_t* w_split
     p.Wx = w_split;
     p.Kp = (a->K + 31) / 32 * 32;
     const int epi = a->epilogue;
-    const bool pair = epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION;
     hipStream_t s = as_stream(stream);
-    int rc;
-    if (try_rows_x3(p, a->batch, epi, s, &rc)) return rc;
-#ifdef VASR_X3_FORCE_CFG
-    const int cfg = VASR_X3_FORCE_CFG;  // diagnostic builds only
-#else
-    const int cfg = pick_x3(a->M, a->N, a->batch, pair);
-#endif
-    switch (cfg) {
+    switch (select_kernel(a->M, a->N, a->K, a->ldc, a->batch, epi, false)) {
+        case kRows: return launch_rows_x3(p, epi, s);
         case 0: return launch_cfg<2, 2, 2, 2, RING_BIG, 3>(p, a->batch, epi, s);
         case 1: return launch_cfg<4, 1, 1, 2, RING_BIG, 3>(p, a->batch, epi, s);
         default: return launch_cfg<2, 2, 1, 1, RING_SMALL, 3>(p, a->batch, epi, s);
@@ -531,16 +543,27 @@ VASR_API int vasr_linear_bf16(const vasr_gemm_args* a, const uint16_t* w_packed,
     p.Wx = w_packed;
     p.Kp = (a->K + 31) / 32 * 32;
     const int epi = a->epilogue;
-    const bool pair = epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION;
     hipStream_t s = as_stream(stream);
-#ifdef VASR_BF16_FORCE_CFG
-    const int cfg = VASR_BF16_FORCE_CFG;  // diagnostic builds only
-#else
-    const int cfg = pick_x3(a->M, a->N, a->batch, pair);
-#endif
-    switch (cfg) {
+    switch (select_kernel(a->M, a->N, a->K, a->ldc, a->batch, epi, true)) {
         case 0: return launch_cfg<2, 2, 2, 2, RING_B16, 1>(p, a->batch, epi, s);
         case 1: return launch_cfg<4, 1, 1, 2, RING_B16, 1>(p, a->batch, epi, s);
         default: return launch_cfg<2, 2, 1, 1, RING_B16, 1>(p, a->batch, epi, s);
     }
+}
+
+VASR_API int vasr_gemm_tile(int M, int N, int K, int batch, int epilogue, int bf16) {
+    using namespace vasr;
+    VASR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 4 == 0 && batch >= 1, "vasr_gemm_tile: bad shape M=%d N=%d K=%d batch=%d",
+                   M, N, K, batch);
+    VASR_CHECK_ARG(epilogue >= VASR_EPI_NONE && epilogue <= VASR_EPI_ARGMAX, "vasr_gemm_tile: unknown epilogue %d",
+                   epilogue);
+    VASR_CHECK_ARG(bf16 == 0 || bf16 == 1, "vasr_gemm_tile: bf16 must be 0 or 1");
+    const bool pair = epilogue == VASR_EPI_PAIR_POWER || epilogue == VASR_EPI_PAIR_FUSION;
+    VASR_CHECK_ARG(!pair || N % 64 == 0, "vasr_gemm_tile: paired epilogue needs N %% 64 == 0");
+    // a dense C: ldc = N columns, or ceil(N / 32) key slots for ARGMAX
+    const int64_t ldc = epilogue == VASR_EPI_ARGMAX ? (N + 31) / 32 : N;
+    const int k = select_kernel(M, N, K, ldc, batch, epilogue, bf16 != 0);
+    if (k == kRows) return 1;
+    const TileCfg& c = kCfgs[k];
+    return c.bm() * 1000 + c.bn();
 }

@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VASR_LIB overrides the library path (diagnostic builds of the same sources, tools/).
 LIB_PATH = os.environ.get("VASR_LIB") or os.path.join(_HERE, "lib", "libvasr_hip.so")
@@ -56,6 +56,7 @@ _SIGNATURES = {
     "vasr_linear_bf16": ([ctypes.POINTER(GemmArgs), c_p, c_p], ctypes.c_int),
     "vasr_pack_weights_bf16": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p], ctypes.c_int),
     "vasr_pack_weights_bf16_elems": ([ctypes.c_int, ctypes.c_int], c_i64),
+    "vasr_gemm_tile": ([ctypes.c_int] * 6, ctypes.c_int),
     "vasr_layer_norm_f32": ([c_p, c_i64, c_p, c_p, c_p, c_i64, ctypes.c_int, ctypes.c_int, c_f32, c_p], ctypes.c_int),
     "vasr_layer_norm_pair_f32": ([c_p, c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_p, c_f32, c_p, c_i64, ctypes.c_int,
                                   ctypes.c_int, c_p], ctypes.c_int),

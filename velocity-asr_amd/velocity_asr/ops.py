@@ -244,6 +244,15 @@ def _linear(args: GemmArgs, w: torch.Tensor, stream) -> None:
         check(L.lib().vasr_linear_x3_f32(args, split_weights(w).data_ptr(), stream), "vasr_linear_x3_f32")
 
 
+def gemm_tile(M: int, N: int, K: int, *, batch: int = 1, epilogue: int = L.EPI_NONE, bf16: bool = False) -> int:
+    """The kernel a gemm / gemm_batched call of this shape launches under the current options
+    (vasr_gemm_tile; host only): 128128, 128064 or 64064 for the tile kernels, 1 for the rows
+    engine.  bf16: the call passes bf16 weights."""
+    k = L.lib().vasr_gemm_tile(int(M), int(N), int(K), int(batch), int(epilogue), int(bool(bf16)))
+    check(min(k, 0), "vasr_gemm_tile")
+    return k
+
+
 def _ln_prologue(a: torch.Tensor, ln) -> torch.Tensor:
     """Row LayerNorm of `a` (vasr_layer_norm_f32) when ln = (weight, bias, eps) is given: the
     LayerNorm feeding a Linear (SSMBlock norm2 -> FFN, the CTC head).  Returns the A the GEMM
