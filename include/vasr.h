@@ -459,6 +459,39 @@ int vasr_pooled_attention_var_f32(const float* q, int64_t ld_q, const float* kv,
                                   int B, int L, int Kp, int heads, int head_dim, const int32_t* kps,
                                   void* stream);
 
+/* ------------------------------------------------------------------ global context, backward (added to ABI 21)
+ * Training through HierarchicalGlobalContext (reference attention.py under autograd): the
+ * gradients of the two kernels above; the forwards are those kernels themselves (only their
+ * inputs are kept).
+ *
+ * vasr_pooled_attention_bwd_f32: with s_k = q . k_k / sqrt(hd), p = softmax(s) over the utterance's
+ * keys (recomputed with the forward's operations), g = d loss / d out, dP_k = g . v_k and
+ * delta = sum_k p_k dP_k (= g . out), per (utterance, head):
+ *   dS_k = p_k (dP_k - delta),           dq   = sum_k dS_k k_k / sqrt(hd),
+ *   dK_k = sum_t dS_tk q_t / sqrt(hd),   dV_k = sum_t p_tk g_t.
+ * q: (B L, A) rows with stride ld_q, kv: (B Kp, 2A) [k | v], dout: (B L, A) contiguous, kps: NULL or
+ * as vasr_pooled_attention_var_f32.  Outputs, contiguous and every element written: dq (B L, A) and
+ * dkv (B Kp, 2A) [dK | dV], rows k >= kps[b] as 0 (L = 0: dkv all 0).  Limits are the forward's:
+ * Kp <= 64, head_dim <= 32, A = heads head_dim <= 256 and a multiple of 4, kv 16-byte aligned,
+ * Kp 2A floats <= 64 KiB.  workspace: vasr_pooled_attention_bwd_workspace_floats(B, L, Kp, heads,
+ * head_dim) floats = B ceil(L / 64) Kp 2A, the [dK | dV] partial of every 64-token tile, and 0 for
+ * L <= 64, where the one tile writes dkv itself (workspace may then be NULL).  No floating-point
+ * atomics: dq has no reduction, a tile's tokens are added in token order and the tiles in tile
+ * order, so the gradients are run-to-run bitwise and an utterance's rows do not depend on the rest
+ * of the batch.  Work is only enqueued on stream. */
+int vasr_pooled_attention_bwd_f32(const float* q, int64_t ld_q, const float* kv, const float* dout,
+                                  float* dq, float* dkv, float* workspace, int64_t workspace_floats,
+                                  int B, int L, int Kp, int heads, int head_dim, const int32_t* kps,
+                                  void* stream);
+int64_t vasr_pooled_attention_bwd_workspace_floats(int B, int L, int Kp, int heads, int head_dim);
+/* vasr_adaptive_pool_bwd_f32: g (B, K, C) = d loss / d out of vasr_adaptive_pool_f32 (lens, ks
+ * NULL) or vasr_adaptive_pool_var_f32 (both given) -> dx (B, L, C), every element written once:
+ *   dx[b,t,c] = sum over the bins i with s_i <= t < e_i, ascending, of g[b,i,c] / (e_i - s_i),
+ * s_i = floor(i L_b / K_b), e_i = ceil((i + 1) L_b / K_b): a gather, at most two bins for K <= L.
+ * Rows t >= lens[b] are written as 0; bins i >= ks[b] of g are never read. */
+int vasr_adaptive_pool_bwd_f32(const float* g, float* dx, int B, int L, int C, int K,
+                               const int32_t* lens, const int32_t* ks, void* stream);
+
 /* ------------------------------------------------------------------ INT8 fake quantisation (C5)
  * FakeQuantize.forward in eval with calibrated buffers (quantize.py:79-97, :118-133):
  *   q = clamp(round_half_even(x / scale + zp), qmin, qmax); x_dq = (q - zp) * scale;

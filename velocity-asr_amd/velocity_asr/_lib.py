@@ -113,6 +113,10 @@ _SIGNATURES = {
     "vasr_ln_adaptive_pool_f32": ([c_p, c_p, c_p, c_f32, c_p] + [ctypes.c_int] * 4 + [c_p, c_p, c_p], ctypes.c_int),
     "vasr_adaptive_pool_f32": ([c_p, c_p] + [ctypes.c_int] * 4 + [c_p], ctypes.c_int),
     "vasr_pooled_attention_f32": ([c_p, c_i64, c_p, c_p] + [ctypes.c_int] * 5 + [c_p], ctypes.c_int),
+    "vasr_pooled_attention_bwd_f32": ([c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p],
+                                      ctypes.c_int),
+    "vasr_pooled_attention_bwd_workspace_floats": ([ctypes.c_int] * 5, c_i64),
+    "vasr_adaptive_pool_bwd_f32": ([c_p, c_p] + [ctypes.c_int] * 4 + [c_p, c_p, c_p], ctypes.c_int),
     "vasr_argmax_f32": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p], ctypes.c_int),
     "vasr_fakequant_f32": ([c_p, c_i64, c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p, ctypes.c_int, c_f32, c_f32,
                             c_p], ctypes.c_int),

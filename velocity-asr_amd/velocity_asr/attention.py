@@ -26,6 +26,108 @@ def _device_ints(values: Sequence[int], device) -> torch.Tensor:
     return torch.tensor([int(v) for v in values], dtype=torch.int32).to(device)
 
 
+def _sizes(values, B: int, device) -> Optional[torch.Tensor]:
+    """None, a host sequence or an int32 device tensor -> the (B,) device array (or None)."""
+    if values is None or isinstance(values, torch.Tensor):
+        return values
+    if len(values) != B:
+        raise ValueError(f"expected {B} per-utterance sizes, got {len(values)}")
+    return _device_ints(values, device)
+
+
+class _PooledAttention(torch.autograd.Function):
+    """out = softmax(q k^T / sqrt(hd)) v per (utterance, head).  Forward: ops.pooled_attention, the
+    inference kernel itself; only q, kv (and the key counts) are saved.  Backward:
+    ops.pooled_attention_bwd, which recomputes the softmax.  Enqueued on the current stream."""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads, kps):
+        B, Lq, A = q.shape
+        Kp = kv.shape[1]
+        with torch.no_grad():
+            q2, kv2 = q.reshape(B * Lq, A), kv.reshape(B * Kp, 2 * A).contiguous()
+            out = ops.pooled_attention(q2, kv2, B, Lq, Kp, heads, kps=kps)
+        ctx.save_for_backward(q2, kv2, *(() if kps is None else (kps,)))
+        ctx.dims = (B, Lq, Kp, A, heads)
+        return out.view(B, Lq, A)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        q2, kv2, *rest = ctx.saved_tensors
+        B, Lq, Kp, A, heads = ctx.dims
+        dq, dkv = ops.pooled_attention_bwd(q2, kv2, g.to(torch.float32).reshape(B * Lq, A).contiguous(), B, Lq, Kp,
+                                           heads, kps=rest[0] if rest else None)
+        need = ctx.needs_input_grad
+        return (dq.view(B, Lq, A) if need[0] else None, dkv.view(B, Kp, 2 * A) if need[1] else None, None, None)
+
+
+def pooled_attention(q: torch.Tensor, kv: torch.Tensor, num_heads: int, key_lengths=None) -> torch.Tensor:
+    """The pooled cross-attention core as a differentiable operator (reference attention.py:143-160,
+    no mask, no dropout): per utterance and head, out = softmax(q k^T / sqrt(head_dim)) v.
+
+    q: (B, Lq, A) and kv: (B, Kp, 2A) holding [K | V], float32 on a HIP device; A = num_heads *
+    head_dim.  key_lengths (host sequence or int32 (B,) device tensor, each in [1, Kp]): utterance b
+    attends over its own first key_lengths[b] keys; the rows of d kv past them are 0.  The value is
+    bitwise ops.pooled_attention (the inference kernel); only q and kv are kept, and the gradients of
+    both come from vasr_pooled_attention_bwd_f32 (no atomics: run-to-run bitwise, an utterance's
+    gradients the same alone and in a batch).  When nothing requires grad the inference kernel runs
+    alone.  Limits are the kernel's: Kp <= 64, head_dim <= 32, A <= 256 and a multiple of 4.
+
+    Query rows are independent, so as with selective_scan the caller zeroes the upstream gradient on
+    the padded frames of a padded batch: the gradients of the keys, values and parameters are then
+    exact."""
+    if q.dim() != 3 or kv.dim() != 3 or kv.shape[0] != q.shape[0] or kv.shape[2] != 2 * q.shape[2] \
+            or q.shape[2] % num_heads:
+        raise ValueError(f"pooled_attention: q {tuple(q.shape)} / kv {tuple(kv.shape)} / {num_heads} heads do not fit")
+    _lib.require_device()
+    B, Lq, A = q.shape
+    kps = _sizes(key_lengths, B, q.device)
+    if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
+        return _PooledAttention.apply(q, kv, num_heads, kps)
+    Kp = kv.shape[1]
+    return ops.pooled_attention(q.detach().reshape(B * Lq, A), kv.detach().reshape(B * Kp, 2 * A), B, Lq, Kp,
+                                num_heads, kps=kps).view(B, Lq, A)
+
+
+class _AdaptiveAvgPool(torch.autograd.Function):
+    """out = adaptive average pooling over time.  Forward: ops.adaptive_pool, the inference kernel;
+    nothing but the sizes is saved (the pooling is linear).  Backward: ops.adaptive_pool_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, K, lens, ks):
+        with torch.no_grad():
+            out = ops.adaptive_pool(x, K, lens=lens, ks=ks)
+        ctx.save_for_backward(*(() if lens is None else (lens, ks)))
+        ctx.L = x.shape[1]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lens, ks = ctx.saved_tensors if ctx.saved_tensors else (None, None)
+        dx = ops.adaptive_pool_bwd(g.to(torch.float32), ctx.L, lens=lens, ks=ks) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None
+
+
+def adaptive_avg_pool(x: torch.Tensor, K: int, lengths=None, sizes=None) -> torch.Tensor:
+    """F.adaptive_avg_pool1d over time as a differentiable operator: (B, L, C) -> (B, K, C), bin i
+    the mean of rows [floor(i L / K), ceil((i + 1) L / K)), 1 <= K <= L.  lengths / sizes (both or
+    neither; host sequences or int32 (B,) device tensors): utterance b pools its first lengths[b]
+    rows into sizes[b] bins, later bins 0, and d x is 0 past lengths[b].  The value is bitwise
+    ops.adaptive_pool; the gradient is vasr_adaptive_pool_bwd_f32, a gather (each element written
+    once, no atomics).  When x does not require grad the inference kernel runs alone."""
+    if x.dim() != 3:
+        raise ValueError(f"adaptive_avg_pool: expected (B, L, C), got {tuple(x.shape)}")
+    if (lengths is None) != (sizes is None):
+        raise ValueError("adaptive_avg_pool: lengths and sizes go together")
+    _lib.require_device()
+    lens, ks = _sizes(lengths, x.shape[0], x.device), _sizes(sizes, x.shape[0], x.device)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _AdaptiveAvgPool.apply(x, int(K), lens, ks)
+    return ops.adaptive_pool(x.detach(), int(K), lens=lens, ks=ks)
+
+
 class AdaptivePool(nn.Module):
     """Adaptive average pooling + learnable projection (reference attention.py:17-78)."""
 
@@ -66,6 +168,23 @@ class AdaptivePool(nn.Module):
         out = ops.gemm(pooled.view(B * pool_size, D), w, b, qparams=qp)
         Q.record(self.pool_proj, out)
         return out.view(B, pool_size, D), (pool_size if lengths is None else sizes)
+
+    def forward_differentiable(self, x: torch.Tensor, prev_pool_size=None,
+                               lengths: Optional[Sequence[int]] = None):
+        """The reference's forward (attention.py:46-78) for training: adaptive_avg_pool (HIP forward
+        and backward), then pool_proj as a torch op.  lengths / prev_pool_size per utterance as in
+        forward; the pooled rows past an utterance's size are pool_proj's bias, which nobody reads."""
+        B, L, D = x.shape
+        if lengths is None:
+            pool_size = min(self._compute_pool_size(L, prev_pool_size), L)
+            pooled = adaptive_avg_pool(x, pool_size)
+        else:
+            prev = prev_pool_size if prev_pool_size is not None else [None] * B
+            sizes = [min(self._compute_pool_size(n, p), n) for n, p in zip(lengths, prev)]
+            pool_size = max(sizes)
+            pooled = adaptive_avg_pool(x, pool_size, lengths=lengths, sizes=sizes)
+        out = torch.nn.functional.linear(pooled, self.pool_proj.weight, self.pool_proj.bias)
+        return out, (pool_size if lengths is None else sizes)
 
 
 class MultiHeadAttention(nn.Module):
@@ -136,6 +255,35 @@ class MultiHeadAttention(nn.Module):
         out = ops.gemm(o, wo, bo, qparams=qpo)
         Q.record(self.out_proj, out)
         return out.view(B, Lq, D)
+
+    def forward_differentiable(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
+                               mask: Optional[torch.Tensor] = None,
+                               key_lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """The reference's forward (attention.py:116-164) for training: the four projections as
+        torch ops on this module's parameters (K and V by one F.linear on [k_proj; v_proj] when key
+        is value), the softmax core as pooled_attention (HIP forward and backward).  The reference
+        drops attention probabilities, which happens inside the fused kernel and is not built:
+        refused in train() with dropout > 0.  key_lengths as in forward; zero the upstream gradient
+        on padded query frames (pooled_attention)."""
+        if mask is not None:
+            raise NotImplementedError("velocity_asr (MI355X build): attention masks are not supported "
+                                      "(the reference path never passes one)")
+        if self.training and self.dropout.p > 0:
+            raise NotImplementedError(
+                "MultiHeadAttention.forward_differentiable: dropout on the attention probabilities acts inside the "
+                f"fused HIP kernel and is not implemented (dropout p={self.dropout.p} in train mode); call eval() on "
+                "this module or build it with dropout=0")
+        F = torch.nn.functional
+        A = self.attention_dim
+        q = F.linear(query, self.q_proj.weight, self.q_proj.bias)
+        if key is value:
+            kv = F.linear(key, torch.cat([self.k_proj.weight, self.v_proj.weight], 0),
+                          torch.cat([self.k_proj.bias, self.v_proj.bias], 0))
+        else:
+            kv = torch.cat([F.linear(key, self.k_proj.weight, self.k_proj.bias),
+                            F.linear(value, self.v_proj.weight, self.v_proj.bias)], -1)
+        o = pooled_attention(q, kv, self.num_heads, key_lengths=key_lengths)
+        return F.linear(o, self.out_proj.weight, self.out_proj.bias)
 
 
 class GatedFusion(nn.Module):
@@ -236,6 +384,16 @@ class GatedFusion(nn.Module):
         Q.record(self.out_proj, out)
         return out.view(B, L, D)
 
+    def forward_differentiable(self, local_features: torch.Tensor, global_features: torch.Tensor) -> torch.Tensor:
+        """The reference's forward (attention.py:191-220) for training, as torch ops on this module's
+        parameters: gate = sigmoid(gate_proj([local | global])), out_proj(gate * local_proj(local) +
+        (1 - gate) * global_proj(global))."""
+        F = torch.nn.functional
+        gate = self.gate_proj(torch.cat([local_features, global_features], dim=-1))
+        local_t = F.linear(local_features, self.local_proj.weight, self.local_proj.bias)
+        global_t = F.linear(global_features, self.global_proj.weight, self.global_proj.bias)
+        return F.linear(gate * local_t + (1 - gate) * global_t, self.out_proj.weight, self.out_proj.bias)
+
 
 class HierarchicalGlobalContext(nn.Module):
     """pool1 -> GlobalSSM -> pool2 -> norm -> cross-attention -> gated fusion (reference attention.py:223-319)."""
@@ -280,3 +438,24 @@ class HierarchicalGlobalContext(nn.Module):
             return self.fusion.forward_attention(local_features, o, self.cross_attention)
         global_context = self.cross_attention(query=query, key=x_pool2, value=x_pool2, key_lengths=kl)
         return self.fusion(local_features, global_context)
+
+    def forward_differentiable(self, local_features: torch.Tensor,
+                               lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """The reference's forward (attention.py:283-319) for training: every stage's
+        forward_differentiable (the poolings and the attention core by their HIP forward and backward
+        kernels, the global stack by GlobalSSM.forward_differentiable), the two LayerNorms as torch
+        ops.  loss.backward() reaches every parameter and local_features.
+
+        lengths: per-utterance token counts of a zero-padded batch; pool sizes and key counts then
+        follow each utterance as in forward, and the global SSM is causal.  As with selective_scan,
+        the caller zeroes the upstream gradient on the padded frames: the gradients of the valid
+        frames and of the parameters are then those of each utterance run alone."""
+        x_pool1, pool_size1 = self.pool1.forward_differentiable(local_features, lengths=lengths)
+        x_ssm = self.global_ssm.forward_differentiable(x_pool1)
+        x_pool2, pool_size2 = self.pool2.forward_differentiable(x_ssm, prev_pool_size=pool_size1,
+                                                                lengths=None if lengths is None else pool_size1)
+        x_pool2 = self.norm1(x_pool2)
+        query = self.norm2(local_features)
+        global_context = self.cross_attention.forward_differentiable(
+            query=query, key=x_pool2, value=x_pool2, key_lengths=None if lengths is None else pool_size2)
+        return self.fusion.forward_differentiable(local_features, global_context)

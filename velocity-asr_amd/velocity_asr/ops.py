@@ -915,6 +915,57 @@ def pooled_attention(q: torch.Tensor, kv: torch.Tensor, B: int, Lq: int, Kp: int
     return out
 
 
+ATTN_BWD_TILE = 64  # tokens per workgroup of the attention's backward (csrc/attn_bwd.hip)
+
+
+def pooled_attention_bwd(q: torch.Tensor, kv: torch.Tensor, dout: torch.Tensor, B: int, Lq: int, Kp: int, heads: int,
+                         kps: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pooled_attention's backward (vasr_pooled_attention_bwd_f32): dout (B*L, A) = d loss / d out ->
+    (dq (B*L, A), dkv (B*Kp, 2A) [dK | dV]), rows past kps[b] of dkv 0.  q, kv, kps as the forward's;
+    the softmax is recomputed.  No atomics: run-to-run bitwise, and an utterance's rows do not depend
+    on the rest of the batch.  workspace: vasr_pooled_attention_bwd_workspace_floats floats (the
+    per-tile [dK | dV] partials; none for L <= 64)."""
+    _cuda_f32("pooled_attention_bwd.q", q)
+    _cuda_f32("pooled_attention_bwd.kv", kv)
+    _cuda_f32("pooled_attention_bwd.dout", dout)
+    M, A, ld_q = _rows("pooled_attention_bwd.q", q)
+    kv, dout = kv.contiguous(), dout.contiguous()
+    if kv.shape != (B * Kp, 2 * A) or M != B * Lq or A % heads or dout.shape != (M, A):
+        raise ValueError("pooled_attention_bwd: inconsistent shapes")
+    kps = _lens("pooled_attention_bwd.kps", kps, B, q.device)
+    dq = torch.empty((M, A), device=q.device, dtype=torch.float32)
+    dkv = torch.empty((B * Kp, 2 * A), device=q.device, dtype=torch.float32)
+    if workspace is None:
+        nws = int(L.lib().vasr_pooled_attention_bwd_workspace_floats(B, Lq, Kp, heads, A // heads))
+        workspace = torch.empty(nws, device=q.device, dtype=torch.float32)
+    _cuda_f32("pooled_attention_bwd.workspace", workspace)
+    ev = _t0("pooled_attention_bwd")
+    check(L.lib().vasr_pooled_attention_bwd_f32(q.data_ptr(), ld_q, kv.data_ptr(), dout.data_ptr(), dq.data_ptr(),
+                                                dkv.data_ptr(), workspace.data_ptr(), workspace.numel(), B, Lq, Kp,
+                                                heads, A // heads, ptr(kps), stream_of(q)),
+          "vasr_pooled_attention_bwd_f32")
+    _t1("pooled_attention_bwd", ev, dict(B=B, L=Lq, Kp=Kp, heads=heads, hd=A // heads))
+    return dq, dkv
+
+
+def adaptive_pool_bwd(g: torch.Tensor, Lq: int, lens: Optional[torch.Tensor] = None,
+                      ks: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """adaptive_pool's backward (vasr_adaptive_pool_bwd_f32): g (B, K, C) = d loss / d out -> dx
+    (B, L, C); with lens / ks rows past lens[b] are 0 and bins past ks[b] of g are not read."""
+    _cuda_f32("adaptive_pool_bwd.g", g)
+    g = g.contiguous()
+    B, K, C = g.shape
+    if (lens is None) != (ks is None):
+        raise ValueError("adaptive_pool_bwd: lens and ks go together")
+    lens = _lens("adaptive_pool_bwd.lens", lens, B, g.device)
+    ks = _lens("adaptive_pool_bwd.ks", ks, B, g.device)
+    dx = torch.empty((B, Lq, C), device=g.device, dtype=torch.float32)
+    check(L.lib().vasr_adaptive_pool_bwd_f32(g.data_ptr(), dx.data_ptr(), B, Lq, C, K, ptr(lens), ptr(ks),
+                                             stream_of(g)), "vasr_adaptive_pool_bwd_f32")
+    return dx
+
+
 def probe_clock(device, blocks: int = 2048, iters: int = 20000) -> dict:
     """Machine state for a benchmark record (vasr_probe_clock): the shader clock over a fixed VALU
     chain (median over workgroups, GHz) and the XCD dispatch order.  The kernels' XCD-aware block

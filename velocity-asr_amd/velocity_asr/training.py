@@ -9,10 +9,14 @@ backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.
 model's own kernels both selective scans have a backward pass too (velocity_asr.ssm.selective_scan: the
 recurrence of scan_mode "sequential" / "mamba", vasr_ssm_scan_save_f32 + vasr_ssm_scan_bwd_f32, and the default
 "parallel" tree, the inference kernel + vasr_ssm_tree_bwd_f32), and SelectiveSSM, SSMBlock, LocalSSMProcessor and
-GlobalSSM have a forward_differentiable built on them; the layers around the scan are GEMM, LayerNorm, conv and
-attention, which torch.autograd differentiates as torch ops.  The rest of training (a whole-model
-forward_differentiable, backward passes of the fused GEMM, tail and LayerNorm kernels, bf16, schedulers, Trainer)
-stays outside this build's scope.
+GlobalSSM have a forward_differentiable built on them.  The global context's two non-GEMM kernels have one as
+well (velocity_asr.attention.pooled_attention and adaptive_avg_pool: the inference kernels forwards,
+vasr_pooled_attention_bwd_f32 and vasr_adaptive_pool_bwd_f32 backwards), and AdaptivePool, MultiHeadAttention,
+GatedFusion and HierarchicalGlobalContext a forward_differentiable built on them (the attention's dropout on its
+probabilities is not built: refused in train mode with dropout > 0).  The layers around these kernels are GEMM,
+LayerNorm, conv and sigmoid, which torch.autograd differentiates as torch ops.  The rest of training (a
+whole-model forward_differentiable, backward passes of the fused GEMM, tail and LayerNorm kernels, bf16,
+schedulers, Trainer) stays outside this build's scope.
 """
 
 from __future__ import annotations
