@@ -361,6 +361,26 @@ int64_t vasr_pack_weights16_bf16_elems(int N, int K);
 int vasr_split_weights16_bf16x3(const float* W, int64_t ldw, int N, int K, uint16_t* out, void* stream);
 int64_t vasr_split_weights16_elems(int N, int K);
 
+/* ------------------------------------------------------------------ gated fusion + head LayerNorm, fused
+ * (added to ABI 21: a new symbol, nothing existing changed)
+ * GatedFusion.forward_attention (attention.py) and the CTC head's LayerNorm (model.py) in one launch
+ * for d_model D = 192 and attention dim A = 48:
+ *   t = local @ w_local^T;  g = o @ w_glob^T                  (both (M, 2D), columns in 32-wide pairs
+ *                                                              [gate | branch] as VASR_EPI_PAIR_FUSION)
+ *   gate = sigmoid((t_gate + g_gate) + b_glob_gate)
+ *   fused = gate * (t_branch + b_local) + (1 - gate) * (g_branch + b_glob_branch)
+ *   out = fused @ w_out^T + b_out;  y = LayerNorm(out; ln_w, ln_b, ln_eps)
+ * local (M, D) and o (M, A) are row views (strides ldl, ldo, multiples of 4, 16-byte aligned);
+ * w_local (2D x D), w_glob (2D x A) and w_out (D x D) are vasr_split_weights_bf16x3 planes, b_glob
+ * (2D) the paired bias, b_local (D).  y (M, D) is always written; out (M, D) only when non-NULL.
+ * t, g and fused never leave the chip.  y and out are bitwise what vasr_linear_x3_f32 (EPI_NONE,
+ * then EPI_PAIR_FUSION with aux = t, then EPI_NONE with bias) and vasr_layer_norm_f32 give.
+ * rows: token rows per workgroup, 32 (6 waves) or 64 (12 waves); 0 chooses by M. */
+int vasr_fusion_tail_f32(const float* local, int64_t ldl, const float* o, int64_t ldo, const uint16_t* w_local,
+                         const uint16_t* w_glob, const float* b_glob, const float* b_local, const uint16_t* w_out,
+                         const float* b_out, const float* ln_w, const float* ln_b, float ln_eps, float* y,
+                         int64_t ldy, float* out, int64_t ldout, int M, int D, int A, int rows, void* stream);
+
 /* ------------------------------------------------------------------ audio I/O (host)
  * load_audio (audio.py:22-62) without torchaudio.  Host functions on host memory (the only
  * entry points here that are not device work): they produce the waveform the front end reads.

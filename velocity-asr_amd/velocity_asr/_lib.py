@@ -93,6 +93,8 @@ _SIGNATURES = {
     "vasr_pack_weights16_bf16_elems": ([ctypes.c_int, ctypes.c_int], c_i64),
     "vasr_split_weights16_bf16x3": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p], ctypes.c_int),
     "vasr_split_weights16_elems": ([ctypes.c_int, ctypes.c_int], c_i64),
+    "vasr_fusion_tail_f32": ([c_p, c_i64, c_p, c_i64] + [c_p] * 8 + [c_f32, c_p, c_i64, c_p, c_i64]
+                             + [ctypes.c_int] * 4 + [c_p], ctypes.c_int),
     "vasr_flac_decode": ([c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p], ctypes.c_int),
     "vasr_resample_length": ([c_i64, ctypes.c_int, ctypes.c_int], c_i64),
     "vasr_resample_f32": ([c_p, ctypes.c_int, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_i64], ctypes.c_int),

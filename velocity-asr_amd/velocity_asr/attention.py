@@ -344,13 +344,29 @@ class GatedFusion(nn.Module):
         return (os.environ.get("VASR_ATTN_COMPOSE", "1") != "0" and all(type(m) is nn.Linear for m in mods)
                 and len({m.weight.dtype for m in mods}) == 1 and mha.out_proj.bias is not None)
 
+    def fusable(self, mha: "MultiHeadAttention", head_norm) -> bool:
+        """forward_attention can run as ops.fusion_tail with head_norm (the LayerNorm that follows)
+        inside: the composed path, fp32 weights, the kernel's widths (d_model 192, attention dim 48), a
+        plain fp32 LayerNorm.  VASR_FUSION_TAIL=0 keeps the three GEMMs and the LayerNorm launch."""
+        return (os.environ.get("VASR_FUSION_TAIL", "1") != "0" and type(head_norm) is nn.LayerNorm
+                and self.composable(mha) and self.out_proj.weight.dtype == torch.float32
+                and head_norm.weight is not None and head_norm.weight.dtype == torch.float32
+                and head_norm.bias is not None and tuple(self.out_proj.weight.shape) == (192, 192)
+                and mha.attention_dim == 48 and self.out_proj.bias is not None and self.local_proj.bias is not None)
+
     def forward_attention(self, local_features: torch.Tensor, o: torch.Tensor,
-                          mha: "MultiHeadAttention") -> torch.Tensor:
-        """forward(local_features, mha's output) from the attention's head outputs o (B * L, A)."""
+                          mha: "MultiHeadAttention", head_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
+        """forward(local_features, mha's output) from the attention's head outputs o (B * L, A).
+        head_norm (extension, only where fusable(mha, head_norm)): head_norm of that, the whole chain
+        in one launch (ops.fusion_tail), bitwise the separate launches."""
         B, L, D = local_features.shape
         local2 = local_features.reshape(B * L, D)
         w_local, _, _, qp = self._paired()
         w_glob, b_glob = self._paired_attention(mha)
+        if head_norm is not None:
+            y, _ = ops.fusion_tail(local2, o, w_local, w_glob, b_glob, self.local_proj.bias, self.out_proj.weight,
+                                   self.out_proj.bias, head_norm.weight, head_norm.bias, head_norm.eps)
+            return y.view(B, L, D)
         t1 = ops.gemm(local2, w_local)
         fused = ops.gemm(o, w_glob, b_glob, epilogue=_lib.EPI_PAIR_FUSION, aux=t1,
                          aux2=self.local_proj.bias, n_out=D, qparams=qp)
@@ -412,12 +428,15 @@ class HierarchicalGlobalContext(nn.Module):
         self.fusion = GatedFusion(d_model=d_model)
 
     def forward(self, local_features: torch.Tensor, lengths: Optional[Sequence[int]] = None,
-                query: Optional[torch.Tensor] = None) -> torch.Tensor:
+                query: Optional[torch.Tensor] = None, head_norm: Optional[nn.LayerNorm] = None):
         """lengths: per-utterance token counts of a zero-padded batch (None: all L).  Pooling
         sizes and attention keys then follow each utterance's own length; the global SSM is
         causal, so the junk rows past an utterance's pooled tokens never reach them.
         query (extension): norm2(local_features) when the caller already has it
-        (LocalSSMProcessor.forward_pair)."""
+        (LocalSSMProcessor.forward_pair).
+        head_norm (extension): the LayerNorm the caller applies next (the CTC head's).  The result is
+        then (rows, normalised): head_norm(fused features) and True where the gated fusion takes it
+        into its own launch (GatedFusion.fusable), else the fused features and False."""
         x_pool1, pool_size1 = self.pool1(local_features, lengths=lengths)
         # VASR_POOL_PRENORM=1: the global stack's final LayerNorm inside the second pooling launch.
         # Bitwise the same, and 3.5 vs 5.3 us graph-timed alone at C2's 32 x 64 -> 16 rows, but C2
@@ -435,9 +454,13 @@ class HierarchicalGlobalContext(nn.Module):
         kl = None if lengths is None else pool_size2
         if self.fusion.composable(self.cross_attention):
             o = self.cross_attention(query=query, key=x_pool2, value=x_pool2, key_lengths=kl, project_out=False)
-            return self.fusion.forward_attention(local_features, o, self.cross_attention)
-        global_context = self.cross_attention(query=query, key=x_pool2, value=x_pool2, key_lengths=kl)
-        return self.fusion(local_features, global_context)
+            if head_norm is not None and self.fusion.fusable(self.cross_attention, head_norm):
+                return self.fusion.forward_attention(local_features, o, self.cross_attention, head_norm), True
+            out = self.fusion.forward_attention(local_features, o, self.cross_attention)
+        else:
+            global_context = self.cross_attention(query=query, key=x_pool2, value=x_pool2, key_lengths=kl)
+            out = self.fusion(local_features, global_context)
+        return out if head_norm is None else (out, False)
 
     def forward_differentiable(self, local_features: torch.Tensor,
                                lengths: Optional[Sequence[int]] = None) -> torch.Tensor:

@@ -125,32 +125,35 @@ class CTCOutputHead(nn.Module):
         super().__init__()
         self.proj = nn.Sequential(nn.LayerNorm(d_model), nn.Dropout(dropout), nn.Linear(d_model, vocab_size))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        B, L, D = x.shape
+    def _ln(self, normalized: bool):
         ln = self.proj[0]
+        return None if normalized else (ln.weight, ln.bias, ln.eps)
+
+    def forward(self, x: torch.Tensor, normalized: bool = False) -> torch.Tensor:
+        """normalized (extension, also argmax / greedy): x is already proj[0](fused features) -- the
+        gated fusion's launch applied it (HierarchicalGlobalContext.forward head_norm=)."""
+        B, L, D = x.shape
         w, b, qp = Q.linear_parts(self.proj[2])
-        # the LayerNorm runs inside the GEMM's A read (identical float operations)
-        logits = ops.gemm(x.reshape(B * L, D), w, b, qparams=qp, ln=(ln.weight, ln.bias, ln.eps))
+        # the LayerNorm is its own launch before the GEMM (ops._ln_prologue)
+        logits = ops.gemm(x.reshape(B * L, D), w, b, qparams=qp, ln=self._ln(normalized))
         Q.record(self.proj[2], logits)
         return logits.view(B, L, w.shape[0])
 
-    def argmax(self, x: torch.Tensor) -> torch.Tensor:
+    def argmax(self, x: torch.Tensor, normalized: bool = False) -> torch.Tensor:
         """argmax over the vocabulary of forward(x), (B, L) int32, fused into the head GEMM: the
         (B, L, V) logits are never written (SURVEY §8 f, rank 1)."""
         B, L, D = x.shape
-        ln = self.proj[0]
         w, b, qp = Q.linear_parts(self.proj[2])
-        return ops.gemm_argmax(x.reshape(B * L, D), w, b, qparams=qp, ln=(ln.weight, ln.bias, ln.eps)).view(B, L)
+        return ops.gemm_argmax(x.reshape(B * L, D), w, b, qparams=qp, ln=self._ln(normalized)).view(B, L)
 
-    def greedy(self, x: torch.Tensor, blank: int = 0, out=None, rows=None):
+    def greedy(self, x: torch.Tensor, blank: int = 0, out=None, rows=None, normalized: bool = False):
         """Greedy CTC decode of forward(x) -- argmax(x) then the collapse of decode.py:46-69 --
         with the argmax and the collapse in one launch after the head GEMM: (tokens (B, L),
         lengths (B,)) int32.  rows: per-utterance row counts (int32 (B,)) of a padded batch."""
         B, L, D = x.shape
-        ln = self.proj[0]
         w, b, qp = Q.linear_parts(self.proj[2])
         toks, lens, _, _ = ops.gemm_ctc_greedy(x.reshape(B * L, D), w, b, B, blank, qparams=qp,
-                                               ln=(ln.weight, ln.bias, ln.eps), out=out, frames=rows)
+                                               ln=self._ln(normalized), out=out, frames=rows)
         return toks, lens
 
 
@@ -204,11 +207,15 @@ class VELOCITYASR(nn.Module):
         return [self.temporal_binding.output_length(f) for f in frames]
 
     def _local_global(self, mel: torch.Tensor, lengths):
-        """mel -> (local features, fused features): the temporal binding, the local stack, then the
-        global context.  The stack's final LayerNorm and the context's query LayerNorm run as one
+        """mel -> (local features, head rows, normalised): the temporal binding, the local stack, then
+        the global context.  The stack's final LayerNorm and the context's query LayerNorm run as one
         launch (VASR_LN_PAIR=0: two), and the temporal binding's LayerNorm inside the first block's
-        norm1 + conv launch (VASR_TB_PRENORM=0: its own launch); bitwise the same either way."""
+        norm1 + conv launch (VASR_TB_PRENORM=0: its own launch); bitwise the same either way.  The
+        CTC head's LayerNorm goes down to the gated fusion: where that takes it into its launch
+        (fp32 model, VASR_FUSION_TAIL=0: never) the head rows are already normalised and the flag,
+        which the head's methods take, is True; else they are the fused features."""
         gc, tb = self.global_context, self.temporal_binding
+        hn = self.ctc_head.proj[0]
         pre = None
         if os.environ.get("VASR_TB_PRENORM", "1") != "0" and type(tb.norm) is nn.LayerNorm:
             x, pre = tb(mel, raw=True), tb.norm
@@ -217,9 +224,9 @@ class VELOCITYASR(nn.Module):
         if os.environ.get("VASR_LN_PAIR", "1") != "0" and type(gc.norm2) is nn.LayerNorm \
                 and type(self.local_ssm.norm) is nn.LayerNorm:
             local, query = self.local_ssm.forward_pair(x, gc.norm2, pre_norm=pre)
-            return local, gc(local, lengths=lengths, query=query)
+            return (local,) + gc(local, lengths=lengths, query=query, head_norm=hn)
         local = self.local_ssm(x, pre_norm=pre)
-        return local, gc(local, lengths=lengths)
+        return (local,) + gc(local, lengths=lengths, head_norm=hn)
 
     def forward(self, mel_spectrogram: torch.Tensor, return_features: bool = False, frames=None):
         """(B, frames, mel_bins) -> CTC logits (B, (frames + 1) // 2, vocab_size).
@@ -235,13 +242,14 @@ class VELOCITYASR(nn.Module):
         mel = mel_spectrogram.to(torch.float32)
         lengths = self._token_lengths(frames, mel.shape[1])
         with torch.no_grad():
+            normalized = False
             if return_features:  # the temporal binding's rows are returned, so they are formed on their own
                 x = self.temporal_binding(mel)
                 local_features = self.local_ssm(x)
                 fused_features = self.global_context(local_features, lengths=lengths)
             else:
-                local_features, fused_features = self._local_global(mel, lengths)
-            logits = self.ctc_head(fused_features)
+                local_features, fused_features, normalized = self._local_global(mel, lengths)
+            logits = self.ctc_head(fused_features, normalized=normalized)
         if return_features:
             return logits, {"temporal_binding": x, "local_features": local_features,
                             "fused_features": fused_features}
@@ -256,8 +264,8 @@ class VELOCITYASR(nn.Module):
             raise RuntimeError("velocity_asr (MI355X build): token_ids needs HIP tensors")
         lengths = self._token_lengths(frames, mel_spectrogram.shape[1])
         with torch.no_grad():
-            x = self._local_global(mel_spectrogram.to(torch.float32), lengths)[1]
-            return self.ctc_head.argmax(x)
+            _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
+            return self.ctc_head.argmax(x, normalized=normalized)
 
     def greedy_token_ids(self, mel_spectrogram: torch.Tensor, frames=None, blank: int = 0, out=None, rows=None):
         """Collapsed greedy CTC tokens of forward(mel) on the device, (tokens (B, L), lengths (B,))
@@ -268,8 +276,8 @@ class VELOCITYASR(nn.Module):
             raise RuntimeError("velocity_asr (MI355X build): greedy_token_ids needs HIP tensors")
         lengths = self._token_lengths(frames, mel_spectrogram.shape[1])
         with torch.no_grad():
-            x = self._local_global(mel_spectrogram.to(torch.float32), lengths)[1]
-            return self.ctc_head.greedy(x, blank, out=out, rows=rows)
+            _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
+            return self.ctc_head.greedy(x, blank, out=out, rows=rows, normalized=normalized)
 
     def get_output_length(self, input_length: int) -> int:
         return (input_length + 1) // 2

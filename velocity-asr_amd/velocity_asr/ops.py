@@ -222,6 +222,36 @@ def ssm_block_tail(g: torch.Tensor, x: torch.Tensor, wo: torch.Tensor, ln_w: tor
     return out
 
 
+def fusion_tail(local: torch.Tensor, o: torch.Tensor, w_local: torch.Tensor, w_glob: torch.Tensor,
+                b_glob: torch.Tensor, b_local: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor,
+                ln_w: torch.Tensor, ln_b: torch.Tensor, ln_eps: float, *, want_out: bool = False, rows: int = 0):
+    """The gated fusion and the LayerNorm that follows it in one launch (vasr_fusion_tail_f32), fp32
+    weights, d_model 192, attention dim 48: (y, out) with out = gemm(fused, w_out, b_out), fused the
+    EPI_PAIR_FUSION blend of gemm(local, w_local) and o @ w_glob.T (paired rows, GatedFusion._paired),
+    and y = layer_norm(out, ln_w, ln_b, ln_eps) -- both bitwise those launches'.  out is formed only
+    when want_out (else None).  rows: 32 or 64 token rows per workgroup, 0 = by M."""
+    for n, t in (("local", local), ("o", o), ("w_local", w_local), ("w_glob", w_glob), ("b_glob", b_glob),
+                 ("b_local", b_local), ("w_out", w_out), ("b_out", b_out), ("ln_w", ln_w), ("ln_b", ln_b)):
+        _cuda_f32(f"fusion_tail.{n}", t)
+    M, D, ldl = _rows("fusion_tail.local", local)
+    Mo, A, ldo = _rows("fusion_tail.o", o)
+    if Mo != M or tuple(w_local.shape) != (2 * D, D) or tuple(w_glob.shape) != (2 * D, A) \
+            or tuple(w_out.shape) != (D, D) or b_glob.numel() != 2 * D \
+            or any(t.numel() != D for t in (b_local, b_out, ln_w, ln_b)):
+        raise ValueError("fusion_tail: inconsistent shapes")
+    y = torch.empty((M, D), device=local.device, dtype=torch.float32)
+    out = torch.empty((M, D), device=local.device, dtype=torch.float32) if want_out else None
+    ev = _t0("fusion_tail")
+    check(L.lib().vasr_fusion_tail_f32(local.data_ptr(), ldl, o.data_ptr(), ldo, split_weights(w_local).data_ptr(),
+                                       split_weights(w_glob).data_ptr(), b_glob.contiguous().data_ptr(),
+                                       b_local.contiguous().data_ptr(), split_weights(w_out).data_ptr(),
+                                       b_out.contiguous().data_ptr(), ln_w.contiguous().data_ptr(),
+                                       ln_b.contiguous().data_ptr(), float(ln_eps), y.data_ptr(), D, ptr(out), D,
+                                       M, D, A, int(rows), stream_of(local)), "vasr_fusion_tail_f32")
+    _t1("fusion_tail", ev, dict(M=M, D=D, A=A))
+    return y, out
+
+
 def pack_bf16(w: torch.Tensor) -> torch.Tensor:
     """One fragment-native bf16 plane (as int16 storage) of a (N, K) bf16 weight view."""
     N, K, ldw = _rows("pack.w", w)
