@@ -82,31 +82,37 @@ def mel_filterbank(n_fft: int = N_FFT, n_mels: int = N_MELS, sample_rate: int = 
     return fb
 
 
-def power_spectrogram(audio: np.ndarray) -> np.ndarray:
+def power_spectrogram(audio: np.ndarray, n_fft: int = N_FFT, hop_length: int = HOP_LENGTH) -> np.ndarray:
     """Reflect pad n_fft//2, framed STFT (center=False), |X|^2 (audio.py:96-115).
     audio (B, S) -> (B, n_fft//2+1, F)."""
-    pad = N_FFT // 2
+    pad = n_fft // 2
     xp = np.pad(audio, ((0, 0), (pad, pad)), mode="reflect")
-    F = (xp.shape[1] - N_FFT) // HOP_LENGTH + 1
-    idx = np.arange(F)[:, None] * HOP_LENGTH + np.arange(N_FFT)[None, :]
-    frames = xp[:, idx] * hann_window()[None, None, :]
+    F = (xp.shape[1] - n_fft) // hop_length + 1
+    idx = np.arange(F)[:, None] * hop_length + np.arange(n_fft)[None, :]
+    frames = xp[:, idx] * hann_window(n_fft)[None, None, :]
     X = np.fft.rfft(frames.astype(f32), axis=-1)
     mag = np.abs(X).astype(f32)
     return np.transpose(mag * mag, (0, 2, 1)).astype(f32)
 
 
-def compute_mel_spectrogram(audio: np.ndarray, normalize: bool = True) -> np.ndarray:
-    """compute_mel_spectrogram (audio.py:65-143): (S,)|(B,S) -> (F,80)|(B,F,80)."""
+def compute_mel_spectrogram(audio: np.ndarray, sample_rate: int = SAMPLE_RATE, n_fft: int = N_FFT,
+                            hop_length: int = HOP_LENGTH, n_mels: int = N_MELS,
+                            normalize: bool = True) -> np.ndarray:
+    """compute_mel_spectrogram (audio.py:65-143): (S,)|(B,S) -> (F,n_mels)|(B,F,n_mels).  A single
+    frame normalises to nan like the reference (unbiased std of one value)."""
     audio = np.asarray(audio, f32)
     squeeze = audio.ndim == 1
     if squeeze:
         audio = audio[None]
-    P = power_spectrogram(audio)
-    mel = np.matmul(mel_filterbank()[None], P).astype(f32)           # audio.py:126
+    P = power_spectrogram(audio, n_fft, hop_length)
+    mel = np.matmul(mel_filterbank(n_fft, n_mels, sample_rate)[None], P).astype(f32)  # audio.py:126
     mel = np.log(mel + f32(1e-10)).astype(f32)                       # audio.py:129
     if normalize:                                                    # audio.py:132-135
         mean = mel.astype(np.float64).mean(axis=-1, keepdims=True).astype(f32)
-        std = mel.astype(np.float64).std(axis=-1, ddof=1, keepdims=True).astype(f32)
+        if mel.shape[-1] > 1:
+            std = mel.astype(np.float64).std(axis=-1, ddof=1, keepdims=True).astype(f32)
+        else:
+            std = np.full_like(mean, np.nan)
         mel = ((mel - mean) / (std + f32(1e-10))).astype(f32)
     mel = np.transpose(mel, (0, 2, 1))
     return np.ascontiguousarray(mel[0] if squeeze else mel)

@@ -97,6 +97,58 @@ def gen_mel():
     save("mel.npz", **out)
 
 
+# the front end off its default geometry: case table and seeded audio (tests/mel_geometry_cases.py)
+_spec = importlib.util.spec_from_file_location("vasr_mel_geometry_cases",
+                                               os.path.join(REPO, "tests", "mel_geometry_cases.py"))
+geo = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(geo)
+
+
+def _mel_fp64(audio, fb, n_fft, hop, normalize):
+    """The reference pipeline (audio.py:96-138) in double: the same float32 window and
+    filterbank values, every operation in fp64."""
+    x = torch.from_numpy(audio).double()
+    pad = n_fft // 2
+    xp = torch.nn.functional.pad(x, (pad, pad), mode="reflect")
+    X = torch.stft(xp, n_fft=n_fft, hop_length=hop, win_length=n_fft, window=torch.hann_window(n_fft).double(),
+                   return_complex=True, center=False)
+    mel = torch.log(torch.matmul(fb.double(), X.abs() ** 2) + 1e-10)
+    if normalize:
+        mel = (mel - mel.mean(dim=-1, keepdim=True)) / (mel.std(dim=-1, keepdim=True) + 1e-10)
+    return mel.transpose(1, 2)
+
+
+def gen_mel_geometry():
+    """mel_geometry.npz: the reference's compute_mel_spectrogram at mel_geometry_cases.CASES for
+    normalize True / False, its filterbank per (n_fft, n_mels, sample_rate), and in meta the
+    reference's own worst |fp32 - fp64| per case over the non-empty filters (fb.sum(1) != 0;
+    an empty filter's row is the constant log(1e-10), whose fp32 mean the reference gets
+    inexactly, so its normalised value there is noise)."""
+    out, own = {}, {}
+    for sr, n_fft, hop, n_mels, S in geo.CASES:
+        name = geo.name(sr, n_fft, hop, n_mels, S)
+        audio = torch.from_numpy(geo.audio(name, S))
+        fb = ref_audio._create_mel_filterbank(n_fft, n_mels, sr, torch.device("cpu"))
+        out[f"fb_{n_fft}_{n_mels}_{sr}"] = fb.numpy()
+        keep = (fb.sum(1) != 0).numpy()
+        err = {}
+        for key, normalize in (("norm", True), ("raw", False)):
+            with torch.no_grad():
+                mel = ref_audio.compute_mel_spectrogram(audio, sample_rate=sr, n_fft=n_fft, hop_length=hop,
+                                                        n_mels=n_mels, normalize=normalize)
+                m64 = _mel_fp64(audio.numpy(), fb, n_fft, hop, normalize)
+            assert mel.shape == (2, S // hop + 1, n_mels), mel.shape
+            out[f"{name}__{key}"] = mel.numpy()
+            d = (mel.double() - m64).abs()[..., keep]
+            err[key] = None if bool(torch.isnan(d).any()) else float(d.max())
+        own[name] = dict(err, frames=S // hop + 1, empty=int((~keep).sum()))
+        print(f"  {name}: {own[name]}")
+    out["meta"] = meta(cases=[list(c) for c in geo.CASES],
+                       audio="tests/mel_geometry_cases.py:audio(name, S): 0.1 * default_rng(crc32(name)).standard_normal((2, S))",
+                       own_fp32_vs_fp64=own)
+    save("mel_geometry.npz", **out)
+
+
 # --------------------------------------------------------------------------- scan
 def scan_inputs(seed, B, L, Di, N):
     rng = np.random.default_rng(seed)
@@ -661,6 +713,8 @@ if __name__ == "__main__":
                              "fullbatch", "cli", "statedims"]
     if "mel" in which:
         gen_mel()
+    if "mel_geometry" in which:  # not in the default list: mel.npz stays as generated
+        gen_mel_geometry()
     if "scan" in which:
         gen_scan()
     if "forward" in which:

@@ -373,7 +373,8 @@ def test_mel_matches_reference(va, name, make, stft, monkeypatch):
     np.testing.assert_array_equal(mel_cpu.numpy(), mel.cpu().numpy())
 
 
-@pytest.mark.parametrize("S_", [201, 400, 1601, 16000, 16333, 160000])
+# 800 .. 5120: F = 6, 7, 10, 12, 16, 32, 33 (6 frames per workgroup, 16 per mel chunk)
+@pytest.mark.parametrize("S_", [201, 400, 1601, 16000, 16333, 160000, 800, 960, 1440, 1760, 2400, 4960, 5120])
 def test_stft_power_fft_vs_fp64(va, S_):
     """Real-FFT power spectrogram vs torch.stft in fp64 (reference audio.py:97-115 in double):
     |P - P64| <= 1e-5 * max(P64) per frame + 1e-6 relative (fp32 FFT rounding)."""

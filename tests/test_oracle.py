@@ -9,6 +9,7 @@ import json
 import numpy as np
 import pytest
 
+import mel_geometry_cases as G
 from conftest import golden, golden_json
 from oracle import velocity_ref as R
 from velocity_asr import synthetic as S
@@ -44,6 +45,69 @@ def test_mel_matches_reference(name, make):
     mel = R.compute_mel_spectrogram(audio)
     assert mel.shape == g[name].shape
     np.testing.assert_allclose(mel, g[name], atol=2e-4, rtol=1e-4)
+
+
+def test_geometry_golden_holds_the_case_table():
+    meta = json.loads(str(golden("mel_geometry.npz")["meta"]))
+    assert [tuple(c) for c in meta["cases"]] == G.CASES
+    assert set(meta["own_fp32_vs_fp64"]) == {G.name(*c) for c in G.CASES}
+
+
+@pytest.mark.parametrize("normalize", [True, False], ids=["norm", "raw"])
+@pytest.mark.parametrize("case", G.CASES, ids=lambda c: G.name(*c))
+def test_mel_geometry_matches_reference(case, normalize):
+    """The oracle with the reference's parameters (sample_rate, n_fft, hop_length, n_mels,
+    normalize) against the reference's output off the default geometry.  Bins of empty filters
+    (taken from the filterbank) are left out of the normalised comparison: their row is the
+    constant log(1e-10), which the oracle's fp64 mean maps to 0 and the reference's fp32 mean to
+    noise; a single frame normalises to nan in both."""
+    sr, n_fft, hop, n_mels, S_ = case
+    g = golden("mel_geometry.npz")
+    name = G.name(*case)
+    want = g[f"{name}__{'norm' if normalize else 'raw'}"]
+    mel = R.compute_mel_spectrogram(G.audio(name, S_), sample_rate=sr, n_fft=n_fft, hop_length=hop,
+                                    n_mels=n_mels, normalize=normalize)
+    assert mel.shape == want.shape == (2, S_ // hop + 1, n_mels)
+    empty = g[f"fb_{n_fft}_{n_mels}_{sr}"].sum(1) == 0
+    if S_ // hop + 1 == 1 and normalize:
+        assert np.isnan(want).all() and np.isnan(mel).all()
+        return
+    assert np.isfinite(mel).all()
+    keep = ~empty if normalize else np.ones(n_mels, bool)
+    np.testing.assert_allclose(mel[..., keep], want[..., keep], atol=2e-4, rtol=1e-4)
+    if normalize:
+        assert not mel[..., empty].any()
+
+
+@pytest.mark.parametrize("case", sorted({(c[1], c[3], c[0]) for c in G.CASES}),
+                         ids=lambda c: "fft%d_mel%d_sr%d" % c)
+def test_filterbanks_match_reference(case):
+    """The package's filterbank is the reference's, bit for bit, at every geometry (the same
+    torch ops in the same order).  The oracle's numpy restatement has the same support and
+    weights within 5e-5: numpy's float32 log10 / pow can differ from torch's vectorised ones by
+    an ulp.  An ulp of mel_max (2^-12 mel near 3800) moves the top band edges by
+    2^-12 * (700 + hz) ln10 / 2595 = 2.5e-3 Hz at 11 kHz, plus an ulp of the edge itself
+    (2^-10 Hz), and a slope divides that by a band half-width of >= 100 Hz there: <= 3.5e-5
+    (measured 1.8e-5 at 22.05 kHz / 128 bins; bit-exact at the default geometry,
+    test_window_and_filterbank_match_reference).  The mel tests above bound its effect."""
+    import torch
+    from velocity_asr import audio as A
+    n_fft, n_mels, sr = case
+    want = golden("mel_geometry.npz")["fb_%d_%d_%d" % case]
+    assert want.shape == (n_mels, n_fft // 2 + 1)
+    np.testing.assert_array_equal(A._create_mel_filterbank(n_fft, n_mels, sr, torch.device("cpu")).numpy(), want)
+    fb = R.mel_filterbank(n_fft, n_mels, sr)
+    np.testing.assert_allclose(fb, want, atol=5e-5, rtol=0)
+    np.testing.assert_array_equal(fb.sum(1) == 0, want.sum(1) == 0)
+
+
+def test_geometry_goldens_empty_filters():
+    """The empty filters (fb.sum(1) == 0) the GPU tests exclude: 4 and 2 bins, on two rows."""
+    g = golden("mel_geometry.npz")
+    got = {G.name(*c): int((g["fb_%d_%d_%d" % (c[1], c[3], c[0])].sum(1) == 0).sum())
+           for c in G.CASES}
+    assert {k: v for k, v in got.items() if v} == {"sr16000_fft400_hop160_mel128_S2560": 4,
+                                                   "sr16000_fft256_hop64_mel80_S1100": 2}
 
 
 @pytest.mark.parametrize("L", [1, 2, 3, 5, 8, 16, 17, 31, 64, 100, 257])
