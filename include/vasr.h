@@ -553,6 +553,24 @@ int vasr_ctc_beam_search(const float* logits, int64_t ld_row, int64_t ld_utt, in
                          double* out_score, int32_t* out_nbeams, void* stream);
 int64_t vasr_ctc_beam_workspace_elems(int L, int W);
 
+/* The same search for padded batches and with a bigram language model; same
+ * outputs, layout ((B, W, L) token rows) and workspace.  With frames and lm_table both NULL it is
+ * vasr_ctc_beam_search.
+ * frames (B, device int32, or NULL = all L): utterance b is searched over its first
+ *   min(max(frames[b], 0), L) rows and no row at or past that count is read; a count of 0 gives
+ *   the single empty beam with score 0.0 (the reference on seq_len = 0).
+ * lm_table ((V + 1, V) float32 with row stride ld_lm >= V, device, or NULL): row 0 holds
+ *   log p(tok | sentence start), row 1 + p holds log p(tok | previous token p); column `blank` and
+ *   row 1 + blank are never read.  Active when lm_table != NULL and lm_weight > 0 (decode.py:188):
+ *   a non-blank candidate whose collapsed prefix is k then scores
+ *   (score + lp[tok]) + lm_weight * S(k), S(k) the float64 left-to-right sum of k's table entries
+ *   -- in every frame, a repeat of the last token included; the blank extension gets no term
+ *   (decode.py:174-193).  lm_weight must not be NaN. */
+int vasr_ctc_beam_search_lm(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                            int W, int blank, const int32_t* frames, const float* lm_table,
+                            int64_t ld_lm, double lm_weight, int32_t* trie, int32_t* out_tokens,
+                            int32_t* out_len, double* out_score, int32_t* out_nbeams, void* stream);
+
 /* Greedy CTC collapse per utterance (decode.py:51-69, :89-123): drop blank (and reset
  * prev), skip repeats of prev if collapse != 0.  out_tokens (B, L) holds each
  * utterance's kept tokens left-aligned, out_len (B) their counts.  If out_start /

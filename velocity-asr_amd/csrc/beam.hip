@@ -16,6 +16,15 @@
 //      i's last token, not an existing node);
 //   4. new extensions get fresh trie nodes.
 // Scores are float64 sums of float32 log-probabilities, as the reference's Python floats.
+//
+// vasr_ctc_beam_search_lm adds two things.  frames: workgroup b walks only its
+// own first min(max(frames[b], 0), L) rows.  lm_table: shallow fusion with a bigram table, the
+// reference's lm_scorer hook (decode.py:187-190): a non-blank candidate of key k scores
+// (score + lp[tok]) + lm_weight * S(k), S(k) the table's score of the whole prefix k, added again
+// in every frame; the blank extension gets no term.  S is carried per live beam (lms[]) next to
+// the prefix's tail token (ptok[]), and a new node's S is S(parent) + table[1 + tail][tok] -- the
+// left-to-right float64 sum the host scorer forms.  The kernel is a template on the LM flag, so
+// the search without a table compiles to what it was.
 #include "vasr_internal.h"
 
 namespace vasr {
@@ -68,14 +77,28 @@ __device__ float block_reduce_f(float v, float* red, bool is_max) {
     return r;
 }
 
+// base + w * S as the reference forms it (token_score += lm_weight * lm_score): a product rounded
+// to float64, then a sum.  Contraction is off here: a fused multiply-add skips the product's
+// rounding and separates candidates that tie exactly in the reference.
+__device__ __forceinline__ double add_lm(double base, double w, double S) {
+#pragma clang fp contract(off)
+    const double term = w * S;
+    return base + term;
+}
+
+template <bool LM>
 __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __restrict__ logits, int64_t ld_row,
                                                                int64_t ld_utt, int L, int V, int W, int blank,
+                                                               const int32_t* __restrict__ frames,
+                                                               const float* __restrict__ lm_table, int64_t ld_lm,
+                                                               double lm_weight,
                                                                int32_t* __restrict__ trie, int64_t trie_stride,
                                                                int32_t* __restrict__ out_tokens,
                                                                int32_t* __restrict__ out_len, double* __restrict__ out_score,
                                                                int32_t* __restrict__ out_nbeams) {
     extern __shared__ __attribute__((aligned(16))) float lp[];  // V log-probabilities
     __shared__ double sc[kMaxBeam], msc[kMaxBeam];
+    __shared__ double lms[LM ? kMaxBeam : 1];  // S(prefix) of every live beam
     __shared__ long long midx[kMaxBeam];
     __shared__ int last[kMaxBeam], node[kMaxBeam], pnode[kMaxBeam], ptok[kMaxBeam], mlast[kMaxBeam];
     __shared__ int src_of[kMaxBeam];  // beam i whose extension reaches beam j's node, or -1
@@ -91,6 +114,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
     const long long VP = (long long)V + 1;
     if (tid == 0) {
         sc[0] = 0.0;
+        lms[0] = 0.0;
         last[0] = -1;  // None
         node[0] = 0;
         pnode[0] = -1;
@@ -101,8 +125,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
         nodes_s = 1;
     }
     __syncthreads();
+    // the clamp is here because a device-resident count is taken without a host look at it
+    const int nf = frames ? min(max(frames[b], 0), L) : L;
 
-    for (int t = 0; t < L; ++t) {
+    for (int t = 0; t < nf; ++t) {
         // 1. log_softmax of row t
         const float* row = lg + (int64_t)t * ld_row;
         float mx = -INFINITY;
@@ -142,9 +168,12 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
                 }
             };
             const int src = src_of[j];
+            // both non-blank candidates keep key j, so both carry lm_weight * S[j]
+            auto lm = [&](double s) { return LM ? add_lm(s, lm_weight, lms[j]) : s; };
             offer(sc[j] + (double)lp[blank], (long long)j * VP, blank);
-            if (last[j] >= 0 && last[j] != blank) offer(sc[j] + (double)lp[last[j]], (long long)j * VP + last[j] + 1, last[j]);
-            if (src >= 0) offer(sc[src] + (double)lp[ptok[j]], (long long)src * VP + ptok[j] + 1, ptok[j]);
+            if (last[j] >= 0 && last[j] != blank)
+                offer(lm(sc[j] + (double)lp[last[j]]), (long long)j * VP + last[j] + 1, last[j]);
+            if (src >= 0) offer(lm(sc[src] + (double)lp[ptok[j]]), (long long)src * VP + ptok[j] + 1, ptok[j]);
             msc[j] = best.s;
             midx[j] = first;
             mlast[j] = bl;
@@ -169,6 +198,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
                         if (src_of[j] == i && ptok[j] == tok) existing = true;
                     if (existing) continue;
                     k.s = sc[i] + (double)lp[tok];
+                    if (LM) {  // row 0 after the sentence start, 1 + tail otherwise; coalesced along tok
+                        const float e = lm_table[(int64_t)(ptok[i] + 1) * ld_lm + tok];
+                        k.s = add_lm(k.s, lm_weight, lms[i] + (double)e);
+                    }
                     k.idx = (long long)i * VP + tok + 1;
                 }
                 // below the previous winner in the sorted order
@@ -184,7 +217,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
         __syncthreads();
         // 4. new beam set, in winner order
         if (tid == 0) {
-            double nsc[kMaxBeam];
+            double nsc[kMaxBeam], nlms[LM ? kMaxBeam : 1];
             int nlast[kMaxBeam], nnode[kMaxBeam], npn[kMaxBeam], npt[kMaxBeam];
             int nodes = nodes_s;
             for (int r = 0; r < nw; ++r) {
@@ -197,6 +230,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
                 if (key_beam >= 0) {
                     const int j = key_beam;
                     nsc[r] = msc[j];
+                    if (LM) nlms[r] = lms[j];
                     nlast[r] = mlast[j];
                     nnode[r] = node[j];
                     npn[r] = pnode[j];
@@ -204,6 +238,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
                 } else {
                     const int tok = pos - 1;
                     nsc[r] = win[r].s;
+                    if (LM) nlms[r] = lms[i] + (double)lm_table[(int64_t)(ptok[i] + 1) * ld_lm + tok];
                     nlast[r] = tok;
                     nnode[r] = nodes;
                     npn[r] = node[i];
@@ -215,6 +250,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
             }
             for (int r = 0; r < nw; ++r) {
                 sc[r] = nsc[r];
+                if (LM) lms[r] = nlms[r];
                 last[r] = nlast[r];
                 node[r] = nnode[r];
                 pnode[r] = npn[r];
@@ -244,17 +280,41 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_kernel(const float* __r
 
 VASR_API int64_t vasr_ctc_beam_workspace_elems(int L, int W) { return 2 * ((int64_t)L * W + 1); }
 
+namespace vasr {
+namespace {
+
+int beam_search(const char* who, const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V, int W,
+                int blank, const int32_t* frames, const float* lm_table, int64_t ld_lm, double lm_weight, int32_t* trie,
+                int32_t* out_tokens, int32_t* out_len, double* out_score, int32_t* out_nbeams, void* stream) {
+    VASR_CHECK_ARG((logits || L == 0) && trie && out_tokens && out_len && out_score && out_nbeams, "%s: null pointer",
+                   who);
+    VASR_CHECK_ARG(B >= 0 && L >= 0 && V >= 1 && V <= 16384 && W >= 1 && W <= kMaxBeam && blank >= 0 && blank < V,
+                   "%s: bad shape B=%d L=%d V=%d W=%d blank=%d", who, B, L, V, W, blank);
+    VASR_CHECK_ARG(!lm_table || ld_lm >= V, "%s: lm_table row stride ld_lm=%lld below V=%d", who, (long long)ld_lm, V);
+    VASR_CHECK_ARG(lm_weight == lm_weight, "%s: lm_weight is NaN", who);
+    if (B == 0) return VASR_OK;
+    const bool lm = lm_table && lm_weight > 0;  // the reference's own test (decode.py:188)
+    hipLaunchKernelGGL(lm ? ctc_beam_kernel<true> : ctc_beam_kernel<false>, dim3(B), dim3(kBeamThreads),
+                       V * sizeof(float), as_stream(stream), logits, ld_row, ld_utt, L, V, W, blank, frames, lm_table,
+                       ld_lm, lm_weight, trie, vasr_ctc_beam_workspace_elems(L, W), out_tokens, out_len, out_score,
+                       out_nbeams);
+    return launch_status(who);
+}
+
+}  // namespace
+}  // namespace vasr
+
 VASR_API int vasr_ctc_beam_search(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V, int W,
                                   int blank, int32_t* trie, int32_t* out_tokens, int32_t* out_len, double* out_score,
                                   int32_t* out_nbeams, void* stream) {
-    using namespace vasr;
-    VASR_CHECK_ARG((logits || L == 0) && trie && out_tokens && out_len && out_score && out_nbeams,
-                   "vasr_ctc_beam_search: null pointer");
-    VASR_CHECK_ARG(B >= 0 && L >= 0 && V >= 1 && V <= 16384 && W >= 1 && W <= kMaxBeam && blank >= 0 && blank < V,
-                   "vasr_ctc_beam_search: bad shape B=%d L=%d V=%d W=%d blank=%d", B, L, V, W, blank);
-    if (B == 0) return VASR_OK;
-    hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(kBeamThreads), V * sizeof(float), as_stream(stream), logits,
-                       ld_row, ld_utt, L, V, W, blank, trie, vasr_ctc_beam_workspace_elems(L, W), out_tokens, out_len,
-                       out_score, out_nbeams);
-    return launch_status("vasr_ctc_beam_search");
+    return vasr::beam_search("vasr_ctc_beam_search", logits, ld_row, ld_utt, B, L, V, W, blank, nullptr, nullptr, 0, 0.0,
+                             trie, out_tokens, out_len, out_score, out_nbeams, stream);
+}
+
+VASR_API int vasr_ctc_beam_search_lm(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V, int W,
+                                     int blank, const int32_t* frames, const float* lm_table, int64_t ld_lm,
+                                     double lm_weight, int32_t* trie, int32_t* out_tokens, int32_t* out_len,
+                                     double* out_score, int32_t* out_nbeams, void* stream) {
+    return vasr::beam_search("vasr_ctc_beam_search_lm", logits, ld_row, ld_utt, B, L, V, W, blank, frames, lm_table,
+                             ld_lm, lm_weight, trie, out_tokens, out_len, out_score, out_nbeams, stream);
 }

@@ -7,7 +7,8 @@ Same command line and printed report as the reference's scripts/evaluate.py:
     python scripts/evaluate.py --checkpoint model.pt --test-set manifest.tsv
 
 --test-set takes a TSV manifest (`audio_path<TAB>reference text`); the reference's
-dataset loader is a stub that loads nothing. --beam-width > 1 selects prefix beam search.
+dataset loader is a stub that loads nothing. --beam-width > 1 selects prefix beam search, one
+launch per batch; --lm FILE.npz --lm-weight X fuses a bigram table (decode.BigramLM.save) into it.
 """
 
 import argparse
@@ -18,6 +19,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from velocity_asr import VELOCITYASR, CTCDecoder, create_default_vocabulary  # noqa: E402
+from velocity_asr.decode import BigramLM  # noqa: E402
 from velocity_asr.training import compute_cer, compute_wer  # noqa: E402
 from velocity_asr.transcription import find_audio_files, load_manifest, transcribe_files  # noqa: E402
 
@@ -37,6 +39,8 @@ def parse_args(argv=None):
     p.add_argument("--device", default="cuda", help="HIP device to run evaluation on")
     p.add_argument("--beam-width", type=int, default=1, help="Beam width for decoding (1 = greedy)")
     p.add_argument("--batch-size", type=int, default=16, help="Max equal-length files per device batch")
+    p.add_argument("--lm", default=None, help="Bigram language model for beam search (.npz of BigramLM.save)")
+    p.add_argument("--lm-weight", type=float, default=0.0, help="Weight of the language model score (0 = off)")
     args = p.parse_args(argv)
     if args.test_set is None and args.audio_dir is None:
         p.error("Either --test-set or --audio-dir must be specified")
@@ -51,12 +55,20 @@ def main(argv=None) -> int:
     model.eval()
     logger.info(f"Model loaded with {model.count_parameters():,} parameters")
     decoder = CTCDecoder(create_default_vocabulary(model.config.vocab_size))
+    lm = None
+    if args.lm:
+        lm = BigramLM.load(args.lm)
+        if lm.vocab_size != model.config.vocab_size:
+            raise SystemExit(f"--lm: table for {lm.vocab_size} tokens, model has {model.config.vocab_size}")
+        if args.beam_width <= 1 or args.lm_weight <= 0:
+            logger.warning("--lm takes effect only with --beam-width > 1 and --lm-weight > 0")
 
     if args.audio_dir:
         files = find_audio_files(args.audio_dir)
         rows = []
         for path, r in zip(files, transcribe_files(model, files, decoder, args.device, False,
-                                                    args.batch_size, args.beam_width)):
+                                                    args.batch_size, args.beam_width, lm=lm,
+                                                    lm_weight=args.lm_weight)):
             if "error" in r:
                 logger.error(f"Error processing {path}: {r['error']}")
                 rows.append((path.name, f"[ERROR: {r['error']}]"))
@@ -81,7 +93,7 @@ def main(argv=None) -> int:
         return 0
     preds, refs = [], []
     results = transcribe_files(model, [a for a, _ in data], decoder, args.device, False,
-                               args.batch_size, args.beam_width)
+                               args.batch_size, args.beam_width, lm=lm, lm_weight=args.lm_weight)
     for (audio, ref), r in zip(data, results):
         if "error" in r:
             logger.error(f"Error processing {audio}: {r['error']}")

@@ -19,6 +19,12 @@ from . import _lib, ops
 
 BLANK_TOKEN = 0
 
+# The package's own __all__ stays the reference's list (tests/test_host.py); extensions are
+# imported from here.
+__all__ = ["BLANK_TOKEN", "DecodingResult", "ctc_greedy_decode", "ctc_greedy_decode_with_timestamps",
+           "ctc_beam_search", "ctc_forced_align", "BigramLM", "CTCDecoder", "create_default_vocabulary",
+           "greedy_token_ids"]
+
 
 @dataclass
 class DecodingResult:
@@ -67,34 +73,126 @@ def ctc_greedy_decode_with_timestamps(logits: torch.Tensor,
     return out
 
 
+class BigramLM:
+    """Bigram language model for shallow fusion in ctc_beam_search (not in the reference, whose
+    lm_scorer is any object with score(tokens)).
+
+    table: float32 (V + 1, V); row 0 is log p(tok | sentence start), row 1 + p is
+    log p(tok | previous token p).  score() is the left-to-right float64 sum of the prefix's
+    entries, so an instance is a valid lm_scorer for the host search and the reference's own; given
+    to ctc_beam_search it is searched on the device from device_table().
+    """
+
+    def __init__(self, table):
+        table = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+        if table.ndim != 2 or table.shape[0] != table.shape[1] + 1 or table.shape[1] < 1:
+            raise ValueError(f"BigramLM: table must be (V + 1, V), got {table.shape}")
+        self.table = table
+        self._device: Dict[Any, torch.Tensor] = {}
+
+    @property
+    def vocab_size(self) -> int:
+        return self.table.shape[1]
+
+    def score(self, tokens: list) -> float:
+        s = 0.0
+        row = 0
+        for tok in tokens:
+            s += float(self.table[row, tok])
+            row = 1 + tok
+        return s
+
+    def device_table(self, device) -> torch.Tensor:
+        """The table on `device`, copied up once."""
+        key = torch.device(device)
+        if key.type == "cuda" and key.index is None:
+            key = torch.device("cuda", torch.cuda.current_device())
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.table).to(key)
+        return self._device[key]
+
+    @classmethod
+    def from_token_sequences(cls, seqs, vocab_size: int, blank: int = BLANK_TOKEN, alpha: float = 1.0) -> "BigramLM":
+        """Add-alpha smoothed bigram counts of token sequences; every row is normalised over the
+        non-blank tokens, and the blank column is -inf (the search never reads it)."""
+        V = int(vocab_size)
+        if not 0 <= blank < V or V < 2:
+            raise ValueError(f"BigramLM: blank {blank} outside a vocabulary of {V} (at least 2 tokens)")
+        if not alpha > 0:
+            raise ValueError("BigramLM: alpha must be positive")
+        counts = np.zeros((V + 1, V), dtype=np.float64)
+        for seq in seqs:
+            row = 0
+            for tok in seq:
+                tok = int(tok)
+                if not 0 <= tok < V or tok == blank:
+                    raise ValueError(f"BigramLM: token {tok} is the blank or outside 0..{V - 1}")
+                counts[row, tok] += 1.0
+                row = 1 + tok
+        counts += alpha
+        counts[:, blank] = 0.0
+        with np.errstate(divide="ignore"):
+            table = np.log(counts) - np.log(counts.sum(axis=1, keepdims=True))
+        return cls(table.astype(np.float32))
+
+    def save(self, path) -> None:
+        """Write the table as a .npz archive; `path` is used as given, so name it *.npz."""
+        with open(path, "wb") as f:
+            np.savez(f, table=self.table)
+
+    @classmethod
+    def load(cls, path) -> "BigramLM":
+        with np.load(path) as z:
+            return cls(z["table"])
+
+
 def ctc_beam_search(logits: torch.Tensor, beam_width: int = 10, blank_token: int = BLANK_TOKEN,
-                    lm_weight: float = 0.0, lm_scorer: Optional[Any] = None) -> List[List[DecodingResult]]:
+                    lm_weight: float = 0.0, lm_scorer: Optional[Any] = None,
+                    input_lengths=None) -> List[List[DecodingResult]]:
     """Prefix beam search (reference decode.py:128-217) on the HIP device.
 
-    Without a language model the whole search runs in vasr_ctc_beam_search (one workgroup
-    per utterance, prefixes as trie nodes, the reference's insertion-order tie rules).  An
-    lm_scorer is a Python callable, so with one (or beam_width > 32) the search runs on the
-    host with the same bookkeeping over device-computed log-probabilities.
+    For widths 1..32 the whole search runs in one launch, one workgroup per utterance, prefixes
+    as trie nodes, the reference's insertion-order tie rules: vasr_ctc_beam_search, or
+    vasr_ctc_beam_search_lm when input_lengths or a BigramLM with lm_weight > 0 is given.
+    input_lengths (B,) are the row counts of a padded batch (a device tensor is taken without a
+    host synchronisation); utterance b is searched over its first input_lengths[b] rows, as the
+    reference on logits[b:b+1, :input_lengths[b]].  A BigramLM is fused on the device with the
+    reference's semantics: lm_weight * lm_scorer.score(prefix) is added to every non-blank
+    candidate in every frame, not to the blank extension.
+
+    Any other lm_scorer is a Python object the device cannot call, so with one (and lm_weight > 0),
+    or with beam_width > 32, the search runs on the host with the same bookkeeping over
+    device-computed log-probabilities -- one score() call per (beam, token, frame).
     """
     logits = _on_device(logits)
-    if (lm_scorer is None or lm_weight <= 0) and 1 <= beam_width <= 32:
-        toks, lens, scores, nb = ops.ctc_beam_search(logits.float(), beam_width, blank_token)
+    lm_on = lm_scorer is not None and lm_weight > 0
+    if (not lm_on or isinstance(lm_scorer, BigramLM)) and 1 <= beam_width <= 32:
+        table = lm_scorer.device_table(logits.device) if lm_on else None
+        toks, lens, scores, nb = ops.ctc_beam_search(logits.float(), beam_width, blank_token, frames=input_lengths,
+                                                     lm_table=table, lm_weight=float(lm_weight) if lm_on else 0.0)
         toks, lens, scores, nb = toks.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy(), nb.cpu().numpy()
         return [[DecodingResult(text="", tokens=toks[b, r, :lens[b, r]].tolist(), score=float(scores[b, r]))
                  for r in range(int(nb[b]))] for b in range(toks.shape[0])]
-    return _ctc_beam_search_host(logits, beam_width, blank_token, lm_weight, lm_scorer)
+    return _ctc_beam_search_host(logits, beam_width, blank_token, lm_weight, lm_scorer, input_lengths)
 
 
 def _ctc_beam_search_host(logits: torch.Tensor, beam_width: int, blank_token: int, lm_weight: float,
-                          lm_scorer: Optional[Any]) -> List[List[DecodingResult]]:
+                          lm_scorer: Optional[Any], input_lengths=None) -> List[List[DecodingResult]]:
     """Host form of the same search (used with a Python lm_scorer)."""
-    log_probs = torch.log_softmax(logits, dim=-1).cpu().numpy().astype(np.float64)
-    B, L, V = log_probs.shape
+    B, L, V = logits.shape
+    if input_lengths is None:
+        frames = [L] * B
+    else:
+        frames = [int(n) for n in (input_lengths.tolist() if isinstance(input_lengths, torch.Tensor) else input_lengths)]
+        if len(frames) != B or any(not 0 <= n <= L for n in frames):
+            raise ValueError(f"ctc_beam_search: input_lengths must be {B} counts in 0..{L}, got {frames}")
     all_results = []
     for b in range(B):
+        # rows past an utterance's count are junk by contract: they are not even normalised
+        log_probs = torch.log_softmax(logits[b, :frames[b]], dim=-1).cpu().numpy().astype(np.float64)
         beams: Dict[Tuple[int, ...], Tuple[float, Optional[int]]] = {(): (0.0, None)}
-        for t in range(L):
-            lp = log_probs[b, t]
+        for t in range(frames[b]):
+            lp = log_probs[t]
             new_beams: Dict[Tuple[int, ...], Tuple[float, Optional[int]]] = {}
             for prefix, (score, last) in beams.items():
                 blank_score = score + lp[blank_token]
@@ -165,8 +263,10 @@ class CTCDecoder:
         seqs = ctc_greedy_decode(logits, blank_token=self.blank_token, collapse_repeated=collapse_repeated)
         return [self._tokens_to_text(t) for t in seqs]
 
-    def decode_beam_search(self, logits: torch.Tensor, beam_width: int = 10, return_all_beams: bool = False):
-        beam_results = ctc_beam_search(logits, beam_width=beam_width, blank_token=self.blank_token)
+    def decode_beam_search(self, logits: torch.Tensor, beam_width: int = 10, return_all_beams: bool = False, *,
+                           input_lengths=None, lm_scorer: Optional[Any] = None, lm_weight: float = 0.0):
+        beam_results = ctc_beam_search(logits, beam_width=beam_width, blank_token=self.blank_token,
+                                       lm_weight=lm_weight, lm_scorer=lm_scorer, input_lengths=input_lengths)
         if return_all_beams:
             for batch_results in beam_results:
                 for result in batch_results:

@@ -1116,9 +1116,15 @@ def minmax(x: torch.Tensor, per_channel: bool = False) -> Tuple[torch.Tensor, to
     return lo1, hi1
 
 
-def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0):
+def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0, *, frames=None, lm_table=None,
+                    lm_weight: float = 0.0):
     """Device prefix beam search over (B, L, V) logits -> (tokens (B, W, L) int32, lengths (B, W),
-    scores (B, W) float64, beams per utterance (B,)), all on the device."""
+    scores (B, W) float64, beams per utterance (B,)), all on the device.
+
+    frames: per-utterance row counts of a padded batch (rows at or past a count are never read; a
+    device tensor is used without a host synchronisation and clamped to 0..L in the kernel, a host
+    sequence must lie in 0..L).  lm_table: (V + 1, V) float32 bigram table (decode.BigramLM), in
+    effect when lm_weight > 0.  With neither, the search is vasr_ctc_beam_search."""
     _cuda_f32("ctc_beam_search.logits", logits)
     if logits.dim() != 3:
         raise ValueError("ctc_beam_search: logits must be (B, L, V)")
@@ -1126,14 +1132,32 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0):
     B, Lq, V = x.shape
     W = int(beam_width)
     dev = x.device
+    fr = tab = None
+    if frames is not None:
+        if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
+            host = torch.as_tensor(frames)
+            if host.numel() and not host.dtype.is_floating_point and (int(host.min()) < 0 or int(host.max()) > Lq):
+                raise ValueError(f"ctc_beam_search.frames: counts must lie in 0..{Lq}, got {host.tolist()}")
+        fr = _ctc_lengths("ctc_beam_search.frames", frames, B, dev, Lq)
+    if lm_table is not None:
+        _cuda_f32("ctc_beam_search.lm_table", lm_table)
+        if tuple(lm_table.shape) != (V + 1, V):
+            raise ValueError(f"ctc_beam_search: lm_table must be ({V + 1}, {V}), got {tuple(lm_table.shape)}")
+        tab = lm_table if lm_table.stride(-1) == 1 else lm_table.contiguous()
     trie = torch.empty(max(B, 1) * int(L.lib().vasr_ctc_beam_workspace_elems(Lq, W)), device=dev, dtype=torch.int32)
     toks = torch.zeros((B, W, max(Lq, 1)), device=dev, dtype=torch.int32)
     lens = torch.zeros((B, W), device=dev, dtype=torch.int32)
     scores = torch.zeros((B, W), device=dev, dtype=torch.float64)
     nbeams = torch.zeros((B,), device=dev, dtype=torch.int32)
-    check(L.lib().vasr_ctc_beam_search(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, W, int(blank), trie.data_ptr(),
-                                       toks.data_ptr(), lens.data_ptr(), scores.data_ptr(), nbeams.data_ptr(),
-                                       stream_of(x)), "vasr_ctc_beam_search")
+    if fr is None and tab is None:
+        check(L.lib().vasr_ctc_beam_search(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, W, int(blank),
+                                           trie.data_ptr(), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                           nbeams.data_ptr(), stream_of(x)), "vasr_ctc_beam_search")
+    else:
+        check(L.lib().vasr_ctc_beam_search_lm(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, W, int(blank), L.ptr(fr),
+                                              L.ptr(tab), 0 if tab is None else tab.stride(0), float(lm_weight),
+                                              trie.data_ptr(), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                              nbeams.data_ptr(), stream_of(x)), "vasr_ctc_beam_search_lm")
     return toks, lens, scores, nbeams
 
 

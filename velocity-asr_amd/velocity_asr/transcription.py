@@ -70,19 +70,21 @@ def group_words(tokens: Sequence[int], spans: Sequence[Tuple[int, int]], vocabul
 
 
 def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: bool,
-                  beam_width: int = 1, lengths: Optional[List[int]] = None) -> List[Tuple[str, Optional[List[Dict]]]]:
+                  beam_width: int = 1, lengths: Optional[List[int]] = None, lm=None,
+                  lm_weight: float = 0.0) -> List[Tuple[str, Optional[List[Dict]]]]:
     """(b, S) device audio -> [(text, words or None)] through the device pipeline.  lengths:
-    per-clip sample counts when the clips were zero-padded to S."""
+    per-clip sample counts when the clips were zero-padded to S.  lm / lm_weight: language model
+    for the beam search (decode.BigramLM runs on the device)."""
     with torch.no_grad():
         mel = mel_on_device(audio, n_mels=model.config.mel_bins, lengths=lengths,
                             frame_pad=model.temporal_binding.conv_padding())
         frames = None if lengths is None else [n // HOP_LENGTH + 1 for n in lengths]
         if beam_width > 1:
             logits = model(mel, frames=frames)
-            if frames is None:
-                return [(t, None) for t in decoder.decode_beam_search(logits, beam_width=beam_width)]
-            return [(decoder.decode_beam_search(logits[b:b + 1, :model.get_output_length(f)],
-                                                beam_width=beam_width)[0], None) for b, f in enumerate(frames)]
+            # one search launch for the batch: each clip's workgroup stops at its own row count
+            rows = None if frames is None else [model.get_output_length(f) for f in frames]
+            return [(t, None) for t in decoder.decode_beam_search(logits, beam_width=beam_width, input_lengths=rows,
+                                                                  lm_scorer=lm, lm_weight=lm_weight)]
         # greedy: the CTC head's GEMM reduces each frame to its argmax (no logits in HBM)
         rows = None
         if frames is not None:
@@ -121,8 +123,9 @@ def _batches(items: List[Tuple[int, torch.Tensor]], batch_size: int, ragged: boo
 
 
 def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timestamps: bool = False,
-                     batch_size: int = 16, beam_width: int = 1) -> List[Dict]:
-    """Transcribe audio files; returns one result dict per file in input order.
+                     batch_size: int = 16, beam_width: int = 1, lm=None, lm_weight: float = 0.0) -> List[Dict]:
+    """Transcribe audio files; returns one result dict per file in input order.  lm / lm_weight:
+    language model for beam_width > 1 (a decode.BigramLM is fused on the device).
 
     A result is {"file", "duration", "transcription"} (+ "words" with timestamps), as the
     reference's transcribe_file returns; a file that fails gets {"file", "error"} instead,
@@ -152,7 +155,7 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
             for j, (_, a) in enumerate(chunk):
                 audio[j, :ns[j]] = a.to(torch.float32)
             decoded = _decode_batch(model, audio.to(dev), decoder, timestamps, beam_width,
-                                    lengths=None if min(ns) == S else ns)
+                                    lengths=None if min(ns) == S else ns, lm=lm, lm_weight=lm_weight)
             for (i, _), n, (text, words) in zip(chunk, ns, decoded):
                 r = {"file": paths[i], "duration": n / SAMPLE_RATE, "transcription": text}
                 if timestamps:
