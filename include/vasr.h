@@ -83,10 +83,19 @@ enum vasr_epilogue {
     VASR_EPI_GELU_PE = 4,       /* C = gelu_erf(acc + bias) + aux[row][col] (pos. enc.) */
     VASR_EPI_PAIR_POWER = 5,    /* W rows paired in 32s (re|im): C[row][k] = re^2+im^2 */
     VASR_EPI_PAIR_FUSION = 6,   /* W rows paired (gate|global): gated fusion, see doc  */
-    VASR_EPI_ARGMAX = 7         /* row argmax of acc + bias (after qparams), no logits write:
+    VASR_EPI_ARGMAX = 7,        /* row argmax of acc + bias (after qparams), no logits write:
                                    C is (rows, ldc) uint64 partial keys, one per 32 columns
                                    (ldc >= ceil(N/32)), every slot written; decode with
                                    vasr_argmax_keys (ties -> first index, decode.py:46) */
+    VASR_EPI_LSE = 9            /* (8 is unassigned and refused.)
+                                   row log-sum-exp of acc + bias, no logits write (fp32 GEMM
+                                   only, no qparams; it runs on the engine the plain epilogue
+                                   gets at that shape, vasr_gemm_tile): C is (rows, ldc) 8-byte slots
+                                   as ARGMAX, each a float pair {m, s}: m the maximum of a group
+                                   of the row's columns, s the sum of exp(v - m) over them, or
+                                   the neutral {-inf, 0}; every slot written with plain stores;
+                                   columns >= N count as -inf, a -inf bias entry is allowed.
+                                   Fold a row's pairs with vasr_lse_combine_f32 */
 };
 
 typedef struct vasr_gemm_args {
@@ -694,6 +703,39 @@ int vasr_ctc_grad_logits_f32(const float* logits, int64_t ld_row, int64_t ld_utt
                              const int32_t* targets, int Smax, const int32_t* frames, const int32_t* tlen,
                              int blank, const float* occ, const float* scale, int32_t* workspace,
                              int64_t workspace_elems, float* grad, void* stream);
+
+/* ------------------------------------------------------------------ CTC loss on the head, no logits
+ * The loss of logits = xn W^T + bias (the CTC head: xn (B * L, K) its normalised rows, W (V, K))
+ * without a (B, L, V) tensor.  Forward: vasr_linear_x3_f32 with VASR_EPI_LSE, vasr_lse_combine_f32,
+ * vasr_ctc_head_emissions_f32, then vasr_ctc_loss[_alpha]_f32 / vasr_ctc_align_f32 as before.
+ * Backward: vasr_ctc_occupancy_f32 once, then per chunk of whole utterances the plain GEMM into a
+ * (rows, V) buffer and vasr_ctc_grad_logits_stats_f32 in place on it.
+ *
+ * vasr_lse_combine_f32: the pairs of a VASR_EPI_LSE GEMM ((M, ld) 8-byte slots, `slots` =
+ * ceil(N/32) used, ld >= slots) -> stats (M, 2) contiguous fp32 {Ms, lse}: Ms the row maximum (0 if
+ * the whole row is -inf), lse = log(sum exp(x - Ms)), so log_softmax(x) = (x - Ms) - lse. */
+int vasr_lse_combine_f32(const float* pairs, int64_t ld, int slots, int M, float* stats, void* stream);
+
+/* emis (B, L, Smax + 1) with vasr_ctc_emissions_f32's meaning from xn (row b * L + t at xn +
+ * (b * L + t) * ld_x), W (row stride ldw), bias ([V] or NULL) and stats (B * L, 2):
+ *   emis[b][t][j] = ((xn[b][t] . W[tok_j] + bias[tok_j]) - Ms) - lse, tok_0 = blank, tok_j = targets[b][j-1];
+ * -inf for a token outside [0, V).  Rows t >= frames[b] are not read; they and slots j > tlen[b] are
+ * left unwritten.  The dot products are accumulated in fp64 and the emission rounded once; they equal
+ * the GEMM's logits to the GEMM's own tolerance, not bitwise.  One workgroup per (utterance, 64 frames) holds its
+ * rows of xn in LDS, 65 * K * 4 bytes: a K that needs more than 64 KiB is VASR_EUNSUPPORTED. */
+int vasr_ctc_head_emissions_f32(const float* xn, int64_t ld_x, const float* W, int64_t ldw, const float* bias,
+                                const float* stats, int B, int L, int V, int K, const int32_t* targets, int Smax,
+                                const int32_t* frames, const int32_t* tlen, int blank, float* emis, void* stream);
+
+/* vasr_ctc_grad_logits_f32 in place, with the rows' {Ms, lse} read from stats (B * L, 2) instead of
+ * recomputed: `logits` holds the logits on entry and the gradient on return (rows t >= T: exact
+ * zeros, never read).  A target column ends as fma(-scale, summed occupancy, scale * softmax), one
+ * rounding of scale * softmax away from vasr_ctc_grad_logits_f32's scale * (softmax - sum).
+ * workspace as vasr_ctc_grad_logits_f32. */
+int vasr_ctc_grad_logits_stats_f32(float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                                   const float* stats, const int32_t* targets, int Smax, const int32_t* frames,
+                                   const int32_t* tlen, int blank, const float* occ, const float* scale,
+                                   int32_t* workspace, int64_t workspace_elems, void* stream);
 
 #ifdef __cplusplus
 }

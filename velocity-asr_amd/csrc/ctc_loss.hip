@@ -740,3 +740,262 @@ VASR_API int vasr_ctc_grad_logits_f32(const float* logits, int64_t ld_row, int64
                        frames, tlen, blank, occ, workspace, scale, grad);
     return launch_status("vasr_ctc_grad_logits_f32");
 }
+
+// ------------------------------------------------------------------ the loss on the head, without logits
+//
+// The CTC head's logits are xn W^T + bias with xn the head's normalised rows.  The loss needs, per
+// row, the log-sum-exp over the vocabulary and the blank's and the target tokens' logits:
+//   - the GEMM with VASR_EPI_LSE (gemm_common.h) leaves one {m, s} pair per 32 columns of each row;
+//     lse_combine_kernel folds a row's pairs into stats[row] = {Ms, lse}, row_lse's two values;
+//   - ctc_head_emissions_kernel recomputes only the Smax + 1 needed logits per row as dot products
+//     of the fp32 inputs accumulated in fp64, and writes the emissions vasr_ctc_emissions_f32
+//     would have gathered;
+//   - ctc_grad_logits_stats_kernel is the logit gradient over one chunk of recomputed logits, in
+//     place, with the row statistics read from stats.
+namespace vasr {
+namespace {
+
+constexpr int kCombineWaves = 4;
+
+__global__ __launch_bounds__(kCombineWaves* kWave) void lse_combine_kernel(const float2* __restrict__ pairs, int64_t ld,
+                                                                           int slots, int M, float* __restrict__ stats) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t r = (int64_t)blockIdx.x * kCombineWaves + (threadIdx.x >> 6);
+    if (r >= M) return;
+    const float2* row = pairs + r * ld;
+    // running (m, s) per lane over slots lane, lane + 64, ...; then the 64 lanes as row_lse does
+    float m = -INFINITY, s = 0.f;
+    for (int j = lane; j < slots; j += kWave) {
+        const float2 e = row[j];
+        const float mn = fmaxf(m, e.x);
+        const float ms = mn == -INFINITY ? 0.f : mn;
+        s = s * fast_exp(m - ms) + e.y * fast_exp(e.x - ms);
+        m = mn;
+    }
+    const float Mx = wave_max(m);
+    const float Ms = Mx == -INFINITY ? 0.f : Mx;
+    const float lse = logf(wave_sum(s * fast_exp(m - Ms)));
+    if (lane == 0) reinterpret_cast<float2*>(stats)[r] = make_float2(Ms, lse);
+}
+
+constexpr int kHeadRows = 64;     // frames per workgroup: one per lane
+constexpr int kHeadWaves = 8;     // waves per workgroup, each on its own tokens
+constexpr int kHeadTok = 4;       // tokens a wave carries through one pass over K
+constexpr int kHeadLds = 65536;   // bytes of LDS a workgroup may ask for
+
+// One workgroup per (utterance, block of 64 frames).  The block's rows of xn sit in LDS k-major,
+// xs[k][row] with rows padded to 65 floats: the staging writes (lanes along k) and the dot
+// products' reads (lanes along rows) are both conflict-free.  Lane = frame; a wave takes four
+// tokens at a time, whose W rows are wave-uniform (scalar loads), so every W row is read once per
+// block and every LDS read feeds four multiply-adds.  The products are accumulated in fp64 and the
+// emission is rounded once: a token's logit then carries no error of its own into the lattice.  (A
+// per-frame error, as the one of lse, shifts every path alike and cancels in the occupancy; a
+// per-token error of fp32-dot size does not, and showed in the gradient: DESIGN.md §4.)
+__global__ __launch_bounds__(kHeadWaves* kWave) void ctc_head_emissions_kernel(
+    const float* __restrict__ xn, int64_t ld_x, const float* __restrict__ W, int64_t ldw,
+    const float* __restrict__ bias, const float* __restrict__ stats, int L, int V, int K,
+    const int32_t* __restrict__ targets, int Smax, const int32_t* __restrict__ frames,
+    const int32_t* __restrict__ tlen, int blank, float* __restrict__ emis) {
+    extern __shared__ float xs[];
+    constexpr int LDR = kHeadRows + 1;
+    const int blocks_per_utt = (L + kHeadRows - 1) / kHeadRows;
+    const int b = blockIdx.x / blocks_per_utt, t0 = (blockIdx.x - b * blocks_per_utt) * kHeadRows;
+    const int T = min(max(frames[b], 0), L);
+    if (t0 >= T) return;  // uniform: padding rows are never read
+    const int nrows = min(kHeadRows, T - t0);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const float* xb = xn + ((int64_t)b * L + t0) * ld_x;
+    for (int i = threadIdx.x; i < nrows * K; i += kHeadWaves * kWave) {
+        const int row = i / K, k = i - row * K;
+        xs[k * LDR + row] = xb[(int64_t)row * ld_x + k];
+    }
+    __syncthreads();
+    if (lane >= nrows) return;  // no barrier below
+
+    const int64_t r = (int64_t)b * L + t0 + lane;
+    const float Ms = stats[2 * r], lse = stats[2 * r + 1];
+    float* e = emis + r * (int64_t)(Smax + 1);
+    const int n = min(max(tlen[b], 0), Smax);
+    const int32_t* tg = targets + (int64_t)b * Smax;
+    const float* xl = xs + lane;
+    for (int j0 = wave * kHeadTok; j0 <= n; j0 += kHeadWaves * kHeadTok) {
+        int tok[kHeadTok];
+        const float* w[kHeadTok];
+        double a[kHeadTok];
+#pragma unroll
+        for (int q = 0; q < kHeadTok; ++q) {
+            const int j = min(j0 + q, n);  // past the last slot: slot n again, not stored
+            tok[q] = j == 0 ? blank : tg[j - 1];
+            // a token id outside [0, V) is not used as an index: its emission is -inf
+            w[q] = W + (int64_t)((tok[q] >= 0 && tok[q] < V) ? tok[q] : 0) * ldw;
+            a[q] = 0.0;
+        }
+#pragma unroll 8
+        for (int k = 0; k < K; ++k) {
+            const double x = (double)xl[k * LDR];
+#pragma unroll
+            for (int q = 0; q < kHeadTok; ++q) a[q] = __builtin_fma(x, (double)w[q][k], a[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < kHeadTok; ++q) {
+            if (j0 + q > n) break;
+            const bool ok = tok[q] >= 0 && tok[q] < V;
+            double v = a[q];
+            if (bias) v += (double)bias[ok ? tok[q] : 0];
+            e[j0 + q] = ok ? (float)((v - (double)Ms) - (double)lse) : -INFINITY;
+        }
+    }
+}
+
+// ctc_grad_logits_kernel over a buffer that holds the logits and receives the gradient (x), with
+// the row's Ms and lse read from stats (no pass for them).  Each lane reads an element before it
+// writes it.  The target columns: pass one left sc * softmax there, so the final value is that
+// minus sc * (the token's summed occupancy), one fused multiply-add on the stored value -- the
+// original logit is not needed again (within one rounding of sc * softmax of the unfused
+// kernel's sc * (softmax - sum)).  Padding rows: exact zeros, never read.
+__global__ __launch_bounds__(kEmisWaves* kWave) void ctc_grad_logits_stats_kernel(
+    float* x, int64_t ld_row, int64_t ld_utt, int B, int L, int V, const float* __restrict__ stats,
+    const int32_t* __restrict__ targets, int Smax, const int32_t* __restrict__ frames,
+    const int32_t* __restrict__ tlen, int blank, const float* __restrict__ occ, const int32_t* __restrict__ chain,
+    const float* __restrict__ scale) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t r = (int64_t)blockIdx.x * kEmisWaves + (threadIdx.x >> 6);
+    const bool inside = r < (int64_t)B * L;
+    const int b = inside ? (int)(r / L) : 0, t = (int)(r - (int64_t)b * L);
+    const bool valid = inside && t < min(max(frames[b], 0), L);  // a predicate: the barrier below is for every wave
+    float* row = x + (int64_t)b * ld_utt + (int64_t)t * ld_row;
+    const int nfull = V >> 2, nch = (nfull + kWave - 1) / kWave;
+    const bool wide = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    float sc = 0.f;
+
+    if (inside && !valid) {
+        for (int c = 0; c < nch; ++c) {
+            const int g = c * kWave + lane;
+            if (g >= nfull) break;
+            if (wide) {
+                reinterpret_cast<float4*>(row)[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                row[4 * g] = row[4 * g + 1] = row[4 * g + 2] = row[4 * g + 3] = 0.f;
+            }
+        }
+        if (lane < (V & 3)) row[4 * nfull + lane] = 0.f;
+    }
+    if (valid) {
+        const float Ms = stats[2 * r], lse = stats[2 * r + 1];
+        sc = scale[b];
+#pragma unroll 4
+        for (int c = 0; c < nch; ++c) {
+            const int g = c * kWave + lane;
+            if (g < nfull) {
+                float4 q;
+                if (wide) {
+                    q = reinterpret_cast<const float4*>(row)[g];
+                } else {
+                    q = make_float4(row[4 * g], row[4 * g + 1], row[4 * g + 2], row[4 * g + 3]);
+                }
+                q.x = sc * fast_exp((q.x - Ms) - lse);
+                q.y = sc * fast_exp((q.y - Ms) - lse);
+                q.z = sc * fast_exp((q.z - Ms) - lse);
+                q.w = sc * fast_exp((q.w - Ms) - lse);
+                if (wide) {
+                    reinterpret_cast<float4*>(row)[g] = q;
+                } else {
+                    row[4 * g] = q.x, row[4 * g + 1] = q.y, row[4 * g + 2] = q.z, row[4 * g + 3] = q.w;
+                }
+            }
+        }
+        if (lane < (V & 3)) row[4 * nfull + lane] = sc * fast_exp((row[4 * nfull + lane] - Ms) - lse);
+    }
+    // the target columns below are updated by other lanes: this wave's stores above have to be
+    // complete first (the barrier waits for them)
+    __syncthreads();
+    if (valid) {
+        const int E = Smax + 1;
+        const int n = min(max(tlen[b], 0), Smax);
+        const int32_t* tg = targets + (int64_t)b * Smax;
+        const int32_t* ch = chain + (int64_t)b * E;
+        const float* oc = occ + r * (int64_t)E;
+        for (int j = lane; j <= n; j += kWave) {
+            const int32_t c = ch[j];
+            if (c < 0) continue;  // a later slot of its token, or a token outside [0, V)
+            float sum = oc[j];    // this token's slots in ascending order
+            for (int k = c; k != 0; k = ch[k] & 0x7fffffff) sum += oc[k];
+            const int v = j == 0 ? blank : tg[j - 1];
+            row[v] = __builtin_fmaf(-sc, sum, row[v]);
+        }
+    }
+}
+
+}  // namespace
+}  // namespace vasr
+
+VASR_API int vasr_lse_combine_f32(const float* pairs, int64_t ld, int slots, int M, float* stats, void* stream) {
+    using namespace vasr;
+    VASR_CHECK_ARG(pairs && stats, "vasr_lse_combine_f32: null pointer");
+    VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(pairs) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
+                   "vasr_lse_combine_f32: pairs and stats must be 8-byte aligned");
+    VASR_CHECK_ARG(M >= 0 && slots >= 1 && ld >= slots, "vasr_lse_combine_f32: bad shape M=%d slots=%d ld=%lld", M, slots,
+                   (long long)ld);
+    if (M == 0) return VASR_OK;
+    hipLaunchKernelGGL(lse_combine_kernel, dim3((M + kCombineWaves - 1) / kCombineWaves), dim3(kCombineWaves * kWave), 0,
+                       as_stream(stream), reinterpret_cast<const float2*>(pairs), ld, slots, M, stats);
+    return launch_status("vasr_lse_combine_f32");
+}
+
+VASR_API int vasr_ctc_head_emissions_f32(const float* xn, int64_t ld_x, const float* W, int64_t ldw, const float* bias,
+                                         const float* stats, int B, int L, int V, int K, const int32_t* targets,
+                                         int Smax, const int32_t* frames, const int32_t* tlen, int blank, float* emis,
+                                         void* stream) {
+    using namespace vasr;
+    VASR_CHECK_ARG(xn && W && stats && frames && tlen && emis && (targets || Smax == 0),
+                   "vasr_ctc_head_emissions_f32: null pointer");
+    VASR_CHECK_ARG(B >= 0 && L >= 1 && L <= kMaxFrames && V >= 1 && K >= 1 && Smax >= 0 && ld_x >= K && ldw >= K,
+                   "vasr_ctc_head_emissions_f32: bad shape B=%d L=%d (1..%d) V=%d K=%d Smax=%d ld_x=%lld ldw=%lld", B, L,
+                   kMaxFrames, V, K, Smax, (long long)ld_x, (long long)ldw);
+    VASR_CHECK_ARG(blank >= 0 && blank < V, "vasr_ctc_head_emissions_f32: blank=%d outside [0, %d)", blank, V);
+    if (Smax > kMaxTarget) {
+        set_error("vasr_ctc_head_emissions_f32: Smax=%d above the supported %d", Smax, kMaxTarget);
+        return VASR_EUNSUPPORTED;
+    }
+    const int64_t lds = (int64_t)K * (kHeadRows + 1) * 4;
+    if (lds > kHeadLds) {
+        set_error("vasr_ctc_head_emissions_f32: K=%d needs %lld bytes of LDS for a block of %d rows, %d available", K,
+                  (long long)lds, kHeadRows, kHeadLds);
+        return VASR_EUNSUPPORTED;
+    }
+    if (B == 0) return VASR_OK;
+    const int blocks = B * ((L + kHeadRows - 1) / kHeadRows);
+    hipLaunchKernelGGL(ctc_head_emissions_kernel, dim3(blocks), dim3(kHeadWaves * kWave), (size_t)lds, as_stream(stream),
+                       xn, ld_x, W, ldw, bias, stats, L, V, K, targets, Smax, frames, tlen, blank, emis);
+    return launch_status("vasr_ctc_head_emissions_f32");
+}
+
+VASR_API int vasr_ctc_grad_logits_stats_f32(float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                                            const float* stats, const int32_t* targets, int Smax, const int32_t* frames,
+                                            const int32_t* tlen, int blank, const float* occ, const float* scale,
+                                            int32_t* workspace, int64_t workspace_elems, void* stream) {
+    using namespace vasr;
+    VASR_CHECK_ARG(logits && stats && frames && tlen && occ && scale && workspace && (targets || Smax == 0),
+                   "vasr_ctc_grad_logits_stats_f32: null pointer");
+    VASR_CHECK_ARG(B >= 0 && L >= 1 && L <= kMaxFrames && V >= 1 && Smax >= 0 && ld_row >= V,
+                   "vasr_ctc_grad_logits_stats_f32: bad shape B=%d L=%d (1..%d) V=%d Smax=%d ld_row=%lld", B, L,
+                   kMaxFrames, V, Smax, (long long)ld_row);
+    VASR_CHECK_ARG(blank >= 0 && blank < V, "vasr_ctc_grad_logits_stats_f32: blank=%d outside [0, %d)", blank, V);
+    if (Smax > kMaxTarget) {
+        set_error("vasr_ctc_grad_logits_stats_f32: Smax=%d above the supported %d", Smax, kMaxTarget);
+        return VASR_EUNSUPPORTED;
+    }
+    VASR_CHECK_ARG(workspace_elems >= (int64_t)B * (Smax + 1),
+                   "vasr_ctc_grad_logits_stats_f32: workspace of %lld int32, %lld needed", (long long)workspace_elems,
+                   (long long)B * (Smax + 1));
+    if (B == 0) return VASR_OK;
+    hipLaunchKernelGGL(ctc_chain_kernel, dim3(B), dim3(kChainThreads), 0, as_stream(stream), targets, Smax, tlen, blank,
+                       V, workspace);
+    const int64_t rows = (int64_t)B * L;
+    hipLaunchKernelGGL(ctc_grad_logits_stats_kernel, dim3((unsigned)((rows + kEmisWaves - 1) / kEmisWaves)),
+                       dim3(kEmisWaves * kWave), 0, as_stream(stream), logits, ld_row, ld_utt, B, L, V, stats, targets,
+                       Smax, frames, tlen, blank, occ, workspace, scale);
+    return launch_status("vasr_ctc_grad_logits_stats_f32");
+}

@@ -220,6 +220,65 @@ __device__ __forceinline__ void epilogue_body(const GemmParams& p, const Tile& t
                 }
             }
         }
+    } else if constexpr (EPI == VASR_EPI_LSE) {
+        // per row: this lane's (maximum m, sum s of exp(v - m)) over its TN columns, then the
+        // 32-lane combine (m, s) + (m', s') = (M, s exp(m - M) + s' exp(m' - M)), M = max(m, m'),
+        // through the ARGMAX transpose; the pair goes to slot s0 of the wave's TN slots, the
+        // neutral pair {-inf, 0} to the others: every slot of the row is written (plain stores).
+        // A column past N counts as -inf; an all--inf set keeps s = 0 (no inf - inf).
+        float2* __restrict__ pairs = reinterpret_cast<float2*>(p.C) + (int64_t)t.bz * p.stride_c;
+        float2* scr2 = reinterpret_cast<float2*>(scr);
+        const int s0 = (n0 + wc * 32 * TN) / 32;
+        float bv[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            const int col = n0 + wc * 32 * TN + tn * 32 + r;
+            const bool ok = !GUARD || col < p.N;
+            bv[tn] = ok ? (p.bias ? p.bias[col] : 0.0f) : -INFINITY;
+        }
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                float v[TN];
+                float m = -INFINITY;
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    v[tn] = acc[tm][tn][i] + bv[tn];
+                    m = fmaxf(m, v[tn]);
+                }
+                const float ms = m == -INFINITY ? 0.f : m;
+                float s = 0.f;
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) s += fast_exp(v[tn] - ms);
+                scr2[((i & 3) + 8 * (i >> 2) + 4 * h) * 33 + r] = make_float2(m, s);
+            }
+            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+            __builtin_amdgcn_wave_barrier();
+            // lane (r, h) combines half h of row r: the maximum first, then one exp per entry
+            float2 e[16];
+            float M = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                e[j] = scr2[r * 33 + 16 * h + j];
+                M = fmaxf(M, e[j].x);
+            }
+            M = fmaxf(M, __shfl_xor(M, 32, 64));
+            const float Ms = M == -INFINITY ? 0.f : M;
+            float S = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) S += e[j].y * fast_exp(e[j].x - Ms);
+            S += __shfl_xor(S, 32, 64);
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+            __builtin_amdgcn_wave_barrier();  // all reads done before the next tm overwrites scr
+            const int row = m0 + wr * 32 * TM + tm * 32 + r;
+            if (!GUARD || row < p.M) {
+#pragma unroll
+                for (int sl = h; sl < TN; sl += 2)  // h = 0 writes the pair, h = 1 the neutral slots
+                    if (!GUARD || (s0 + sl) * 32 < p.N)
+                        pairs[(int64_t)row * p.ldc + s0 + sl] = sl == 0 ? make_float2(M, S) : make_float2(-INFINITY, 0.f);
+            }
+        }
     } else {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
@@ -259,7 +318,8 @@ __device__ __forceinline__ void epilogue_body(const GemmParams& p, const Tile& t
 }
 
 // scr: optional per-wave LDS scratch of 32 x 33 uint64 for the ARGMAX row reduction (the
-// staging LDS is free once the main loop is done); null selects the DPP reduction.
+// staging LDS is free once the main loop is done); null selects the DPP reduction.  LSE needs it
+// (32 x 33 float pairs).
 template <int BM, int BN, int TM, int TN, int EPI>
 __device__ __forceinline__ void epilogue(const GemmParams& p, const Tile& t, floatx16 (&acc)[TM][TN], int wr,
                                          int wc, int r, int h, unsigned long long* scr = nullptr) {
@@ -290,10 +350,16 @@ inline int check_args(const vasr_gemm_args* a, const char* fn, GemmParams& p) {
                    "%s: K, lda, stride_a must be multiples of 4 (K=%d lda=%lld)", fn, a->K, (long long)a->lda);
     VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->A) & 15) == 0, "%s: A must be 16-byte aligned", fn);
     const int epi = a->epilogue;
-    VASR_CHECK_ARG(epi >= VASR_EPI_NONE && epi <= VASR_EPI_ARGMAX, "%s: unknown epilogue %d", fn, epi);
+    VASR_CHECK_ARG((epi >= VASR_EPI_NONE && epi <= VASR_EPI_ARGMAX) || epi == VASR_EPI_LSE, "%s: unknown epilogue %d", fn,
+                   epi);
     if (epi == VASR_EPI_ARGMAX)
         VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->C) & 7) == 0 && a->ldc >= (a->N + 31) / 32,
                        "%s: argmax keys must be 8-byte aligned with ldc >= ceil(N / 32) slots", fn);
+    if (epi == VASR_EPI_LSE) {
+        VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->C) & 7) == 0 && a->ldc >= (a->N + 31) / 32,
+                       "%s: lse pairs must be 8-byte aligned with ldc >= ceil(N / 32) slots", fn);
+        VASR_CHECK_ARG(a->qparams == nullptr, "%s: qparams not allowed with LSE", fn);
+    }
     const bool pair = epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION;
     if (pair)
         VASR_CHECK_ARG(a->N % 64 == 0 && a->n_out > 0 && a->n_out <= a->N / 2,

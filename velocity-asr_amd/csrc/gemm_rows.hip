@@ -403,6 +403,13 @@ __device__ __forceinline__ void role_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// a float from the lane a DPP control names (gemm::dpp_u64's float form, every row and bank)
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+    const int i = (int)__float_as_uint(v);
+    return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(i, i, CTRL, 0xF, 0xF, false));
+}
+
 // rows_epilogue's per-element arithmetic (same operations, same order)
 template <int EPI, int SP>
 __device__ __forceinline__ float rows_value(const GemmParams& p, float v, float bv, const float4& qc, int row, int col) {
@@ -469,6 +476,42 @@ __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buf
             const int off = (c4 == 0 && row < p.M) ? (row * (int)p.ldc + slot) * 8 : OOB16;
             typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             const u32x2 kv = {(unsigned)key, (unsigned)(key >> 32)};
+            __builtin_amdgcn_raw_buffer_store_b64(kv, cbuf, off, 0, VASR_ROWS_STORE_AUX);
+        }
+        return;
+    }
+    if constexpr (EPI == VASR_EPI_LSE) {
+        // the chunk is the row's slot n0 / 32: {m, s} = the maximum of acc + bias over its 32
+        // columns and the sum of exp(v - m), a column past N counting as -inf (gemm_common.h's
+        // pair; the host refuses qparams).  The row's 8 lanes agree on the maximum first (ARGMAX's
+        // three DPP steps), so each element costs one exp and the sums add without rescaling; an
+        // all--inf slot subtracts 0 and leaves the neutral pair {-inf, 0}.
+        const int slot = n0 / 32;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int row = m0 + 8 * s + rl;
+            const float4 x = *reinterpret_cast<const float4*>(tile + (8 * s + rl) * 32 + c4);
+            const float xv[4] = {x.x, x.y, x.z, x.w};
+            float v[4];
+            float m = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = col0 + e < p.N ? xv[e] + bv[e] : -INFINITY;
+                m = fmaxf(m, v[e]);
+            }
+            m = fmaxf(m, dpp_f32<0xB1>(m));
+            m = fmaxf(m, dpp_f32<0x4E>(m));
+            m = fmaxf(m, dpp_f32<0x141>(m));
+            const float ms = m == -INFINITY ? 0.f : m;
+            float sum = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sum += fast_exp(v[e] - ms);
+            sum += dpp_f32<0xB1>(sum);
+            sum += dpp_f32<0x4E>(sum);
+            sum += dpp_f32<0x141>(sum);
+            const int off = (c4 == 0 && row < p.M) ? (row * (int)p.ldc + slot) * 8 : OOB16;
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            const u32x2 kv = {__float_as_uint(m), __float_as_uint(sum)};
             __builtin_amdgcn_raw_buffer_store_b64(kv, cbuf, off, 0, VASR_ROWS_STORE_AUX);
         }
         return;
@@ -638,7 +681,8 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the tables are in LDS before B_0
         if (dma)
             for (int j = 0; j < DEPTH && j < nc; ++j) issue(j);
-        const int c_bytes = (EPI == VASR_EPI_ARGMAX ? 8 : 4) * ((p.M - 1) * (int)p.ldc + (EPI == VASR_EPI_ARGMAX ? NT : p.N));
+        constexpr bool SLOTS = EPI == VASR_EPI_ARGMAX || EPI == VASR_EPI_LSE;  // C is 8-byte slots, one per chunk
+        const int c_bytes = (SLOTS ? 8 : 4) * ((p.M - 1) * (int)p.ldc + (SLOTS ? NT : p.N));
         const __amdgpu_buffer_rsrc_t cbuf = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, c_bytes, 0x00020000);
         auto epilogue = [&](int j) {  // chunk j's tiles of compute waves sw, sw + SWV, ...
             if (!stores) return;
@@ -735,7 +779,7 @@ int launch_roles(const GemmParams& p, int epi, hipStream_t s) {
     int groups, per;
     pick_groups(row_blocks, NT, &groups, &per);
     // 16-byte stores need every lane's 4 columns valid together and 16-byte aligned
-    const int wide = epi != VASR_EPI_ARGMAX && p.N % 4 == 0 && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
+    const int wide = epi != VASR_EPI_ARGMAX && epi != VASR_EPI_LSE && p.N % 4 == 0 && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
     const dim3 grid(row_blocks * groups), block(64 * (CWV + MWV));
 #define VASR_R(E) hipLaunchKernelGGL((gemm_rows_roles_kernel<KS, E>), grid, block, 0, s, p, groups, per, wide)
     switch (epi) {
@@ -745,6 +789,7 @@ int launch_roles(const GemmParams& p, int epi, hipStream_t s) {
         case VASR_EPI_RESIDUAL: VASR_R(VASR_EPI_RESIDUAL); break;
         case VASR_EPI_GELU_PE: VASR_R(VASR_EPI_GELU_PE); break;
         case VASR_EPI_ARGMAX: VASR_R(VASR_EPI_ARGMAX); break;
+        case VASR_EPI_LSE: VASR_R(VASR_EPI_LSE); break;
         default: set_error("vasr_linear_x3_f32: rows engine: epilogue %d not supported", epi); return VASR_EINVAL;
     }
 #undef VASR_R
@@ -779,18 +824,22 @@ int launch_rows(const GemmParams& p, int epi, hipStream_t s) {
 // nothing: vasr_linear_x3_f32 and vasr_gemm_tile both ask it); false when the tile kernel should run.
 bool rows_x3_selected(int M, int N, int Kp, int64_t ldc, int batch, int epi) {
     if (batch != 1 || Kp > 192 || M <= 0 || epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION) return false;
+    if (epi == VASR_EPI_LSE && !VASR_ROWS_ROLES) return false;  // only the wave-specialised kernel has that epilogue
     if (Kp != 128 && Kp != 192) return false;  // the W chunk stride is Kp / 16 k-steps
     // raw-buffer C addressing: the valid bytes must fit the 31-bit offsets
-    if ((int64_t)M * ldc * (epi == VASR_EPI_ARGMAX ? 8 : 4) >= ((int64_t)1 << 31) - 64) return false;
+    if ((int64_t)M * ldc * (epi == VASR_EPI_ARGMAX || epi == VASR_EPI_LSE ? 8 : 4) >= ((int64_t)1 << 31) - 64) return false;
     const int engine = option(VASR_OPT_GEMM_ENGINE);  // 0 auto, 1 tiles, 2 rows
     if (engine == 1) return false;
     // auto: the rows engine where it measured faster (profiles/r03l: K = 192, N >= 512 -- the
     // composed head GEMM 35.8 vs 45.6 us, in_proj 21.1 vs 22.8; at N = 384 / 192 a block's short
     // chunk run does not amortise its A load; one utterance, M = 501: 13.2 vs 8.4 us in the
     // graph, profiles/r03m -- two 256-row blocks per column group); the argmax head keeps the tiles (its per-chunk
-    // 32-lane reductions), and so do the residual / GELU+PE epilogues (they spill at 8 waves)
+    // 32-lane reductions), and so do the residual / GELU+PE epilogues (they spill at 8 waves).  The row
+    // log-sum-exp epilogue goes where the plain one goes: the loss's GEMM then runs on the engine its
+    // logits would have been written by, with 1/16 of the stores (profiles/ctc_head.md)
     if (engine == 0 && (Kp != 192 || N < 512 || M < 4096 ||
-                        !(epi == VASR_EPI_NONE || epi == VASR_EPI_GELU || epi == VASR_EPI_SOFTPLUS_FROM)))
+                        !(epi == VASR_EPI_NONE || epi == VASR_EPI_GELU || epi == VASR_EPI_SOFTPLUS_FROM ||
+                          epi == VASR_EPI_LSE)))
         return false;
     return true;
 }

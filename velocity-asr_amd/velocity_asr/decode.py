@@ -217,6 +217,28 @@ def _ctc_beam_search_host(logits: torch.Tensor, beam_width: int, blank_token: in
     return all_results
 
 
+def _align_targets(targets, target_lengths, blank_token: int):
+    """A list of token lists as a blank-padded (B, Smax) int32 tensor, with its lengths unless given."""
+    if not isinstance(targets, torch.Tensor):
+        rows = [list(r) for r in targets]
+        if target_lengths is None:
+            target_lengths = [len(r) for r in rows]
+        width = max((len(r) for r in rows), default=0)
+        targets = torch.tensor([r + [blank_token] * (width - len(r)) for r in rows], dtype=torch.int32).reshape(
+            len(rows), width)
+    return targets, target_lengths
+
+
+def _align_emissions(emis, tg, frames, tlen):
+    """The Viterbi lattice over emissions (ops.ctc_emissions' or ops.ctc_head_emissions') as
+    ctc_forced_align's result."""
+    state, st, en, score = ops.ctc_align(emis, tg, frames, tlen)
+    state, st, en, score = state.cpu().numpy(), st.cpu().numpy(), en.cpu().numpy(), score.cpu().numpy()
+    tlen = tlen.cpu().numpy().clip(0, tg.shape[1])
+    return [(float(score[b]), [(int(s), int(e)) for s, e in zip(st[b, :tlen[b]], en[b, :tlen[b]])],
+             state[b].tolist()) for b in range(emis.shape[0])]
+
+
 def ctc_forced_align(logits: torch.Tensor, targets, input_lengths=None, target_lengths=None,
                      blank_token: int = BLANK_TOKEN) -> List[Tuple[float, List[Tuple[int, int]], List[int]]]:
     """CTC forced alignment of a KNOWN transcript: the most probable path through the CTC lattice
@@ -234,20 +256,8 @@ def ctc_forced_align(logits: torch.Tensor, targets, input_lengths=None, target_l
     logits = _on_device(logits)
     if logits.dim() != 3:
         raise ValueError("ctc_forced_align: logits must be (B, L, V)")
-    B, Lq, _ = logits.shape
-    if not isinstance(targets, torch.Tensor):
-        rows = [list(r) for r in targets]
-        if target_lengths is None:
-            target_lengths = [len(r) for r in rows]
-        width = max((len(r) for r in rows), default=0)
-        targets = torch.tensor([r + [blank_token] * (width - len(r)) for r in rows], dtype=torch.int32).reshape(
-            len(rows), width)
-    emis, tg, frames, tlen = ops.ctc_emissions(logits, targets, input_lengths, target_lengths, blank_token)
-    state, st, en, score = ops.ctc_align(emis, tg, frames, tlen)
-    state, st, en, score = state.cpu().numpy(), st.cpu().numpy(), en.cpu().numpy(), score.cpu().numpy()
-    tlen = tlen.cpu().numpy().clip(0, tg.shape[1])
-    return [(float(score[b]), [(int(s), int(e)) for s, e in zip(st[b, :tlen[b]], en[b, :tlen[b]])],
-             state[b].tolist()) for b in range(B)]
+    targets, target_lengths = _align_targets(targets, target_lengths, blank_token)
+    return _align_emissions(*ops.ctc_emissions(logits, targets, input_lengths, target_lengths, blank_token))
 
 
 class CTCDecoder:

@@ -156,6 +156,42 @@ class CTCOutputHead(nn.Module):
                                                ln=self._ln(normalized), out=out, frames=rows)
         return toks, lens
 
+    def fusable(self) -> bool:
+        """Whether the loss can run straight from the head's input (ops.ctc_head_emissions): a plain
+        fp32 nn.Linear.  A bf16 or QAT head goes through its logits."""
+        lin = self.proj[2]
+        return type(lin) is nn.Linear and lin.weight.dtype == torch.float32
+
+    def ctc_emissions(self, x: torch.Tensor, targets: torch.Tensor, input_lengths=None, target_lengths=None,
+                      blank: int = 0, normalized: bool = False, fused=None):
+        """ops.ctc_emissions(forward(x), ...) -> (emis (B, L, Smax + 1), targets, frames, tlen),
+        forward-only.  On an fp32 head the (B, L, V) logits are never written: the head GEMM leaves
+        each row's log-sum-exp (VASR_EPI_LSE) and only the blank's and the target tokens' logits are
+        formed.  fused (extension): None = where the head allows it, False = through the logits."""
+        B, L, D = x.shape
+        if fused is None:
+            fused = self.fusable()
+        elif fused and not self.fusable():
+            raise TypeError("CTCOutputHead.ctc_emissions: the logit-free path needs a plain float32 head")
+        with torch.no_grad():
+            if not fused:
+                return ops.ctc_emissions(self.forward(x, normalized=normalized), targets, input_lengths,
+                                         target_lengths, blank)
+            lin = self.proj[2]
+            emis, _, tg, frames, tlen = ops.ctc_head_emissions(x.reshape(B * L, D), lin.weight, lin.bias, targets,
+                                                               input_lengths, target_lengths, blank, B=B,
+                                                               ln=self._ln(normalized))
+        return emis, tg, frames, tlen
+
+    def align(self, x: torch.Tensor, targets, input_lengths=None, target_lengths=None, blank: int = 0,
+              normalized: bool = False):
+        """decode.ctc_forced_align(forward(x), ...) without the logits (ctc_emissions, then the same
+        Viterbi lattice): per utterance (score, [(start_frame, end_frame), ...], frame_labels)."""
+        from .decode import _align_emissions, _align_targets
+
+        targets, target_lengths = _align_targets(targets, target_lengths, blank)
+        return _align_emissions(*self.ctc_emissions(x, targets, input_lengths, target_lengths, blank, normalized))
+
 
 class VELOCITYASR(nn.Module):
     """VELOCITY-ASR v2 (reference model.py:242-471)."""
@@ -278,6 +314,23 @@ class VELOCITYASR(nn.Module):
         with torch.no_grad():
             _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
             return self.ctc_head.greedy(x, blank, out=out, rows=rows, normalized=normalized)
+
+    def ctc_loss(self, mel_spectrogram: torch.Tensor, targets: torch.Tensor, input_lengths, target_lengths, *,
+                 reduction: str = "mean", zero_infinity: bool = True, frames=None, blank: int = 0) -> torch.Tensor:
+        """training.CTCLoss(blank, reduction, zero_infinity)(forward(mel, frames=frames), targets,
+        input_lengths, target_lengths) without the (B, L, V) logits (training.CTCHeadLoss on the head's
+        input): scoring a checkpoint.  Forward-only, eval mode as the inference kernels demand.
+        input_lengths are token-row counts, as CTCLoss takes them."""
+        from .training import CTCHeadLoss
+
+        if mel_spectrogram.device.type != "cuda":
+            _lib.require_device()
+            raise RuntimeError("velocity_asr (MI355X build): ctc_loss needs HIP tensors")
+        lengths = self._token_lengths(frames, mel_spectrogram.shape[1])
+        loss = CTCHeadLoss(self.ctc_head, blank, reduction, zero_infinity)
+        with torch.no_grad():
+            _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
+            return loss(x, targets, input_lengths, target_lengths, normalized=normalized)
 
     def get_output_length(self, input_length: int) -> int:
         return (input_length + 1) // 2

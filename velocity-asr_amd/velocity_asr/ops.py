@@ -1302,3 +1302,119 @@ def ctc_grad_logits(logits: torch.Tensor, occ: torch.Tensor, targets: torch.Tens
                                            chain.data_ptr(), chain.numel(), grad.data_ptr(), stream_of(x)),
           "vasr_ctc_grad_logits_f32")
     return grad
+
+
+def _head_operands(who: str, a: torch.Tensor, w: torch.Tensor, bias, ln):
+    """The fp32 operands of the logit-free head ops: (rows a after the optional LayerNorm, w, bias)."""
+    _cuda_f32(f"{who}.a", a)
+    _cuda_f32(f"{who}.w", w)
+    if bias is not None:
+        _cuda_f32(f"{who}.bias", bias)
+        if bias.dim() != 1 or bias.shape[0] != w.shape[0] or not bias.is_contiguous():
+            raise ValueError(f"{who}: bias must be a contiguous ({w.shape[0]},) tensor")
+    a = _ln_prologue(a, ln)
+    M, K, lda = _rows(f"{who}.a", a)
+    N, Kw, ldw = _rows(f"{who}.w", w)
+    if Kw != K:
+        raise ValueError(f"{who}: a has K={K} but w has K={Kw}")
+    return a, (M, K, lda), (N, ldw)
+
+
+def _gemm_lse_pairs(a: torch.Tensor, w: torch.Tensor, bias, dims, wdims, pairs: Optional[torch.Tensor] = None):
+    """The VASR_EPI_LSE GEMM: (M, ceil(N/32)) float pairs {m, s} of a @ w.T + bias per row."""
+    (M, K, lda), (N, ldw) = dims, wdims
+    slots = (N + 31) // 32
+    if pairs is None:
+        pairs = torch.empty((M, slots, 2), device=a.device, dtype=torch.float32)  # every slot is written
+    args = GemmArgs()
+    args.A, args.lda, args.stride_a = a.data_ptr(), lda, 0
+    args.W, args.ldw = w.data_ptr(), ldw
+    args.bias = ptr(bias)
+    args.C, args.ldc, args.stride_c = pairs.data_ptr(), pairs.stride(0) // 2, 0
+    args.batch, args.M, args.N, args.K = 1, M, N, K
+    args.epilogue = L.EPI_LSE
+    ev = _t0("gemm")
+    _linear(args, w, stream_of(a))
+    _t1("gemm", ev, dict(M=M, N=N, K=K, batch=1))
+    return pairs, slots
+
+
+def lse_combine(pairs: torch.Tensor, slots: int) -> torch.Tensor:
+    """(M, ld, 2) float pairs of a VASR_EPI_LSE GEMM, `slots` used per row -> stats (M, 2) = {Ms, lse}."""
+    _cuda_f32("lse_combine.pairs", pairs)
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or pairs.stride(2) != 1 or pairs.stride(1) != 2:
+        raise ValueError("lse_combine: pairs must be (M, ld, 2) with contiguous slots")
+    M = pairs.shape[0]
+    stats = torch.empty((M, 2), device=pairs.device, dtype=torch.float32)
+    check(L.lib().vasr_lse_combine_f32(pairs.data_ptr(), pairs.stride(0) // 2 if M > 1 else pairs.shape[1], int(slots), M,
+                                       stats.data_ptr(), stream_of(pairs)), "vasr_lse_combine_f32")
+    return stats
+
+
+def gemm_lse(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, ln=None,
+             pairs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """stats (M, 2) = {Ms, lse} of the rows of a @ w.T + bias, fused into the GEMM epilogue
+    (VASR_EPI_LSE) and one small combine: the (M, N) product is never written.  Ms is the row
+    maximum (0 for a row of -inf), lse = log(sum(exp(x - Ms))): log_softmax(x) = (x - Ms) - lse.
+    fp32 weights only.  ln = (weight, bias, eps): LayerNorm each row of `a` first.  pairs: a
+    caller's (M, ld >= ceil(N/32), 2) float32 buffer for the GEMM's partial pairs."""
+    a, dims, wdims = _head_operands("gemm_lse", a, w, bias, ln)
+    if pairs is not None:
+        _cuda_f32("gemm_lse.pairs", pairs)
+        if pairs.dim() != 3 or pairs.shape[0] != dims[0] or pairs.shape[1] < (wdims[0] + 31) // 32 \
+                or pairs.shape[2] != 2 or not pairs.is_contiguous():
+            raise ValueError(f"gemm_lse: pairs must be a contiguous ({dims[0]}, >= {(wdims[0] + 31) // 32}, 2) tensor")
+    pairs, slots = _gemm_lse_pairs(a, w, bias, dims, wdims, pairs)
+    return lse_combine(pairs, slots)
+
+
+def ctc_head_emissions(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], targets: torch.Tensor,
+                       frames=None, tlen=None, blank: int = 0, *, B: int, ln=None):
+    """ctc_emissions of the logits a @ w.T + bias (a: B * L rows, utterance-major) without the
+    logits -> (emis (B, L, Smax + 1), stats (B * L, 2), targets, frames, tlen): the row statistics
+    from gemm_lse, the blank's and the target tokens' logits as dot products accumulated in fp64
+    (vasr_ctc_head_emissions_f32).  Memory does not grow with rows x vocabulary.  fp32 weights only."""
+    a, dims, wdims = _head_operands("ctc_head_emissions", a, w, bias, ln)
+    (M, K, lda), (V, ldw) = dims, wdims
+    if B <= 0 or M % B:
+        raise ValueError(f"ctc_head_emissions: {M} rows do not split into B={B} utterances")
+    Lq = M // B
+    dev = a.device
+    tg = _ctc_targets("ctc_head_emissions", targets, B, dev)
+    Smax = tg.shape[1]
+    fr = _ctc_lengths("ctc_head_emissions.frames", frames, B, dev, Lq)
+    tl = _ctc_lengths("ctc_head_emissions.tlen", tlen, B, dev, Smax)
+    pairs, slots = _gemm_lse_pairs(a, w, bias, dims, wdims)
+    stats = lse_combine(pairs, slots)
+    del pairs
+    emis = torch.empty((B, Lq, Smax + 1), device=dev, dtype=torch.float32)
+    check(L.lib().vasr_ctc_head_emissions_f32(a.data_ptr(), lda, w.data_ptr(), ldw, ptr(bias), stats.data_ptr(), B, Lq, V,
+                                              K, tg.data_ptr(), Smax, fr.data_ptr(), tl.data_ptr(), int(blank),
+                                              emis.data_ptr(), stream_of(a)), "vasr_ctc_head_emissions_f32")
+    return emis, stats, tg, fr, tl
+
+
+def ctc_grad_logits_stats(logits: torch.Tensor, stats: torch.Tensor, occ: torch.Tensor, targets: torch.Tensor, frames,
+                          tlen, scale: torch.Tensor, blank: int = 0) -> torch.Tensor:
+    """ctc_grad_logits in place: `logits` (B, L, V) contiguous holds the logits on entry and the
+    gradient on return (it is returned); the rows' {Ms, lse} come from stats (B * L, 2) instead of a
+    pass over the row."""
+    _cuda_f32("ctc_grad_logits_stats.logits", logits)
+    if logits.dim() != 3 or not logits.is_contiguous():
+        raise ValueError("ctc_grad_logits_stats: logits must be a contiguous (B, L, V) tensor")
+    V = logits.shape[2]
+    B, Lq, Smax, tg, fr, tl = _ctc_lattice_args("ctc_grad_logits_stats", occ, targets, frames, tlen)
+    if tuple(logits.shape[:2]) != (B, Lq):
+        raise ValueError(f"ctc_grad_logits_stats: logits {tuple(logits.shape)} for an occupancy of {B} x {Lq} rows")
+    _cuda_f32("ctc_grad_logits_stats.stats", stats)
+    if stats.numel() != B * Lq * 2 or not stats.is_contiguous():
+        raise ValueError(f"ctc_grad_logits_stats: stats must be a contiguous ({B * Lq}, 2) tensor")
+    _cuda_f32("ctc_grad_logits_stats.scale", scale)
+    if tuple(scale.shape) != (B,) or not scale.is_contiguous():
+        raise ValueError(f"ctc_grad_logits_stats: scale must be a contiguous ({B},) tensor")
+    chain = torch.empty((B, Smax + 1), device=logits.device, dtype=torch.int32)
+    check(L.lib().vasr_ctc_grad_logits_stats_f32(logits.data_ptr(), logits.stride(1), logits.stride(0), B, Lq, V,
+                                                 stats.data_ptr(), tg.data_ptr(), Smax, fr.data_ptr(), tl.data_ptr(),
+                                                 int(blank), occ.data_ptr(), scale.data_ptr(), chain.data_ptr(),
+                                                 chain.numel(), stream_of(logits)), "vasr_ctc_grad_logits_stats_f32")
+    return logits

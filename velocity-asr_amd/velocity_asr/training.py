@@ -5,8 +5,18 @@ metrics scripts/evaluate.py imports (training.py:412-501).
 CTCLoss here is the loss on the HIP path (vasr_ctc_emissions_f32 + vasr_ctc_loss_f32): by default
 forward only, scoring a known transcript; with differentiable=True it also has a backward pass
 (vasr_ctc_loss_alpha_f32 in the forward, vasr_ctc_occupancy_f32 + vasr_ctc_grad_logits_f32 in the
-backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.CTCLoss.  Of the
-model's own kernels both selective scans have a backward pass too (velocity_asr.ssm.selective_scan: the
+backward), so a PyTorch training loop can use it in place of F.log_softmax + nn.CTCLoss.
+
+CTCHeadLoss is the same loss taken one layer earlier, on the CTC head's input: the head's GEMM keeps
+each row's log-sum-exp in its epilogue (VASR_EPI_LSE) and only the blank's and the target tokens'
+logits are formed (vasr_ctc_head_emissions_f32), so neither the (B, L, V) logits nor, with
+differentiable=True, their gradient is ever allocated whole: the backward recomputes the logits a
+chunk of utterances at a time, turns the chunk into its gradient in place
+(vasr_ctc_grad_logits_stats_f32) and contracts it against the weight and the rows at once.  Its
+memory is bounded by chunk_bytes, not by rows x vocabulary ("The loss on the head").
+VELOCITYASR.ctc_loss, CTCOutputHead.ctc_emissions and CTCOutputHead.align are its forward-only users.
+
+Of the model's own kernels both selective scans have a backward pass too (velocity_asr.ssm.selective_scan: the
 recurrence of scan_mode "sequential" / "mamba", vasr_ssm_scan_save_f32 + vasr_ssm_scan_bwd_f32, and the default
 "parallel" tree, the inference kernel + vasr_ssm_tree_bwd_f32), and SelectiveSSM, SSMBlock, LocalSSMProcessor and
 GlobalSSM have a forward_differentiable built on them.  The global context's two non-GEMM kernels have one as
@@ -125,17 +135,181 @@ class CTCLoss(nn.Module):
         return (nll / tlen.clamp(min=1).to(nll.dtype)).mean()
 
     def _pad_concatenated(self, targets: torch.Tensor, target_lengths, B: int) -> torch.Tensor:
-        """1-D concatenated targets -> (B, Smax) rows (host bookkeeping: this form reads the lengths)."""
-        flat = targets[targets != self.blank_token].cpu()
-        lens = [int(n) for n in torch.as_tensor(target_lengths).cpu().tolist()]
-        if len(lens) != B or sum(lens) > flat.numel():
-            raise ValueError(f"CTCLoss: target_lengths {lens} do not fit {flat.numel()} concatenated targets")
-        out = torch.zeros((B, max(lens, default=0)), dtype=torch.int32)
-        pos = 0
-        for b, n in enumerate(lens):
-            out[b, :n] = flat[pos:pos + n]
-            pos += n
-        return out
+        return _pad_concatenated("CTCLoss", targets, target_lengths, B, self.blank_token)
+
+
+def _pad_concatenated(who: str, targets: torch.Tensor, target_lengths, B: int, blank: int) -> torch.Tensor:
+    """1-D concatenated targets -> (B, Smax) rows (host bookkeeping: this form reads the lengths)."""
+    flat = targets[targets != blank].cpu()
+    lens = [int(n) for n in torch.as_tensor(target_lengths).cpu().tolist()]
+    if len(lens) != B or sum(lens) > flat.numel():
+        raise ValueError(f"{who}: target_lengths {lens} do not fit {flat.numel()} concatenated targets")
+    out = torch.zeros((B, max(lens, default=0)), dtype=torch.int32)
+    pos = 0
+    for b, n in enumerate(lens):
+        out[b, :n] = flat[pos:pos + n]
+        pos += n
+    return out
+
+
+class _CTCHeadNll(torch.autograd.Function):
+    """Per-utterance nll (B,) of the head's normalised rows xn (B * L, K), its weight (V, K) and bias,
+    with the gradient to all three and no (B, L, V) tensor.  Forward: ops.ctc_head_emissions + the
+    lattice that keeps alpha.  Backward: the occupancy once, then chunks of whole utterances with
+    rows * V * 4 <= chunk_bytes (at least one utterance; sizes come from shapes, never from
+    lengths): the chunk's logits by the plain GEMM into one reused buffer, their gradient in place,
+    and dX = G W, dW += G^T xn, db += sum G straight from the buffer, each only if its input asks
+    for a gradient (a frozen head forms no dW, db).  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, xn, w, bias, tg, frames, tlen, blank, zero_infinity, B, chunk_bytes):
+        emis, stats, tg, frames, tlen = ops.ctc_head_emissions(xn, w, bias, tg, frames, tlen, blank, B=B)
+        nll, alpha = ops.ctc_loss_alpha(emis, tg, frames, tlen)
+        ctx.save_for_backward(xn, w, bias, emis, alpha, nll, stats, tg, frames, tlen)
+        ctx.blank, ctx.zero_infinity, ctx.chunk_bytes = blank, zero_infinity, chunk_bytes
+        return nll
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_nll):
+        xn, w, bias, emis, alpha, nll, stats, tg, frames, tlen = ctx.saved_tensors
+        B, Lq = emis.shape[0], emis.shape[1]
+        V, K = w.shape
+        scale = grad_nll.to(dtype=torch.float32)
+        infeasible = torch.full_like(scale, 0.0 if ctx.zero_infinity else float("nan"))
+        scale = torch.where(torch.isinf(nll), infeasible, scale).contiguous()
+        occ = ops.ctc_occupancy(emis, alpha, nll, tg, frames, tlen)
+        nb = min(B, max(1, int(ctx.chunk_bytes) // (Lq * V * 4)))
+        buf = torch.empty((nb * Lq, V), device=xn.device, dtype=torch.float32)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        dx = torch.empty((B * Lq, K), device=xn.device, dtype=torch.float32) if need_x else None
+        dw = torch.zeros((V, K), device=xn.device, dtype=torch.float32) if need_w else None
+        db = torch.zeros((V,), device=xn.device, dtype=torch.float32) if need_b and bias is not None else None
+        # rows past frames[b] may hold anything (NaN included): they are zero in G, and zero here
+        live = (torch.arange(Lq, device=xn.device, dtype=torch.int32)[None, :] < frames[:, None]).reshape(B * Lq, 1)
+        wd, stats = w.detach(), stats.view(B * Lq, 2)
+        for b0 in range(0, B, nb):
+            b1 = min(b0 + nb, B)
+            r0, r1 = b0 * Lq, b1 * Lq
+            xc = xn[r0:r1]
+            g = ops.gemm(xc, w, bias, out=buf[:r1 - r0])
+            ops.ctc_grad_logits_stats(g.view(b1 - b0, Lq, V), stats[r0:r1], occ[b0:b1], tg[b0:b1], frames[b0:b1],
+                                      tlen[b0:b1], scale[b0:b1], ctx.blank)
+            if dx is not None:
+                torch.mm(g, wd, out=dx[r0:r1])
+            if dw is not None:
+                dw.addmm_(g.t(), torch.where(live[r0:r1], xc, torch.zeros((), device=xn.device)))
+            if db is not None:
+                db += g.sum(0)
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
+class CTCHeadLoss(nn.Module):
+    """CTCLoss()(head(features), ...) without the logits: the loss straight from the CTC head's
+    input `features` (B, L, d_model), with CTCLoss's signature semantics otherwise (2-D or 1-D
+    concatenated targets, the three reductions, zero_infinity, and inputs that require grad refused
+    unless differentiable=True).
+
+    Forward-only, a plain fp32 head runs ops.ctc_head_emissions; a bf16 or QAT head goes through
+    its logits.  The forward-only value is the eval-mode one: the head's dropout is not applied,
+    whatever head.training says (the differentiable path applies it, as a torch op).  With differentiable=True (fp32 plain heads only; others are refused) the LayerNorm
+    and the dropout are torch ops that autograd differentiates and one autograd.Function covers the
+    Linear and the loss (_CTCHeadNll): gradients reach the features, both LayerNorm parameters, the
+    weight and the bias.  The loss value is the forward-only one, bitwise when the rows it is given
+    are already normalised.
+
+    Args:
+        head: the model's CTCOutputHead (not registered as a submodule)
+        blank_token, reduction, zero_infinity: as CTCLoss
+        differentiable: give inputs that require grad a backward pass instead of refusing them
+        chunk_bytes: the backward's logits buffer, whole utterances, at least one
+        fused: None = the module decides (fused from FUSED_MIN_VOCAB up, and whenever a gradient
+            is asked for: its point is the bounded memory); True / False force a path
+    """
+
+    # forward-only crossover (profiles/ctc_head.md, rows = 16032, where both GEMMs run on the rows
+    # engine): through the logits is faster at V = 1000 (57 vs 89 us) and 2000 (105 vs 122), the two
+    # tie at 3000 (155.6 both), logit-free is faster at 4000 (189 vs 198), 5000 (226 vs 253), 10000
+    # (395 vs 472) and, at 4008 rows on the tile kernels, 50000 (530 vs 710).  The rule reads V alone:
+    # the two GEMMs share an engine at every shape (ops.gemm_tile), so what is left to decide is the
+    # logits' traffic against the gather's fixed cost, measured at this one row count only.
+    FUSED_MIN_VOCAB = 3072
+
+    def __init__(self, head, blank_token: int = 0, reduction: str = "mean", zero_infinity: bool = True, *,
+                 differentiable: bool = False, chunk_bytes: int = 256 << 20, fused=None):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"CTCHeadLoss: {reduction} is not a valid value for reduction")
+        if fused not in (None, True, False):
+            raise ValueError("CTCHeadLoss: fused must be None, True or False")
+        if int(chunk_bytes) <= 0:
+            raise ValueError("CTCHeadLoss: chunk_bytes must be positive")
+        if not all(hasattr(head, a) for a in ("proj", "fusable", "ctc_emissions")):
+            raise TypeError("CTCHeadLoss: head must be a CTCOutputHead")
+        if differentiable and not head.fusable():
+            raise TypeError("CTCHeadLoss: differentiable=True needs a plain float32 head (not bf16, not QAT)")
+        if fused and not head.fusable():
+            raise TypeError("CTCHeadLoss: fused=True needs a plain float32 head (not bf16, not QAT)")
+        object.__setattr__(self, "head", head)  # the model owns it
+        self.blank_token = blank_token
+        self.reduction = reduction
+        self.zero_infinity = zero_infinity
+        self.differentiable = differentiable
+        self.chunk_bytes = int(chunk_bytes)
+        self.fused = fused
+
+    def forward(self, features: torch.Tensor, targets: torch.Tensor, input_lengths: torch.Tensor,
+                target_lengths: torch.Tensor, normalized: bool = False) -> torch.Tensor:
+        """features (B, L, d_model); targets, input_lengths, target_lengths as CTCLoss.forward.
+        normalized (extension): features are already head.proj[0](fused features)."""
+        from .decode import _on_device
+
+        head = self.head
+        lin, ln = head.proj[2], head.proj[0]
+        params = [p for p in (lin.weight, lin.bias, ln.weight, ln.bias) if p is not None]
+        wants = torch.is_grad_enabled() and features.requires_grad
+        if wants and not self.differentiable:
+            raise RuntimeError(
+                "velocity_asr.training.CTCHeadLoss is forward-only unless differentiable=True. "
+                "Call it under torch.no_grad() or on detached features.")
+        # differentiable: also when only the head's own parameters ask for a gradient
+        with_grad = wants or (self.differentiable and torch.is_grad_enabled() and any(p.requires_grad for p in params))
+        if features.dim() != 3:
+            raise ValueError("CTCHeadLoss: features must be (batch, seq_len, d_model)")
+        B, Lq, D = features.shape
+        if targets.dim() == 1:
+            targets = _pad_concatenated("CTCHeadLoss", targets, target_lengths, B, self.blank_token)
+        features = _on_device(features if with_grad else features.detach())
+        dev = features.device
+        fused = self.fused
+        if with_grad:
+            if not head.fusable():
+                raise TypeError("CTCHeadLoss: differentiable=True needs a plain float32 head (not bf16, not QAT)")
+            fused = True if fused is None else fused
+            tg = ops._ctc_targets("CTCHeadLoss", targets, B, dev)
+            frames = ops._ctc_lengths("CTCHeadLoss.input_lengths", input_lengths, B, dev, Lq)
+            tlen = ops._ctc_lengths("CTCHeadLoss.target_lengths", target_lengths, B, dev, tg.shape[1])
+            xn = features.to(torch.float32)
+            xn = head.proj[1](xn if normalized else ln(xn))
+            if fused:
+                nll = _CTCHeadNll.apply(xn.reshape(B * Lq, D), lin.weight, lin.bias, tg, frames, tlen,
+                                        self.blank_token, self.zero_infinity, B, self.chunk_bytes)
+            else:
+                nll = _CTCNll.apply(nn.functional.linear(xn, lin.weight, lin.bias), tg, frames, tlen,
+                                    self.blank_token, self.zero_infinity)
+        else:
+            if fused is None:
+                fused = head.fusable() and lin.weight.shape[0] >= self.FUSED_MIN_VOCAB
+            emis, tg, frames, tlen = head.ctc_emissions(features.to(torch.float32), targets, input_lengths,
+                                                        target_lengths, self.blank_token, normalized, fused=fused)
+            nll = ops.ctc_loss(emis, tg, frames, tlen)
+        if self.zero_infinity:
+            nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
+        if self.reduction == "none":
+            return nll
+        if self.reduction == "sum":
+            return nll.sum()
+        return (nll / tlen.clamp(min=1).to(nll.dtype)).mean()
 
 
 def _edit_distance(a: Sequence, b: Sequence) -> int:
