@@ -109,7 +109,9 @@ def test_fused_block_bf16_model(monkeypatch):
     """The bf16 model's fused tail (vasr_ssm_block_tail_bf16: one bf16 plane, activations
     rounded to bf16 at the MFMA input as vasr_linear_bf16 does) vs the bf16 launches it
     replaces; both round h and f to bf16, so they agree to bf16 rounding of rare boundary
-    cases."""
+    cases.  This bound is a model-level smoke check; the kernel's own bound, per output row against
+    the float64 tail with the same roundings, is test_ssm_tail_kernels_gpu.py's
+    test_bf16_tail_rows_against_staged_fp64."""
     import velocity_asr as va
     from velocity_asr import synthetic as S
     W = S.make_weights(None, seed=0)
