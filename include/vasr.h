@@ -87,7 +87,19 @@ enum vasr_epilogue {
                                    C is (rows, ldc) uint64 partial keys, one per 32 columns
                                    (ldc >= ceil(N/32)), every slot written; decode with
                                    vasr_argmax_keys (ties -> first index, decode.py:46) */
-    VASR_EPI_LSE = 9            /* (8 is unassigned and refused.)
+    VASR_EPI_ARGMAX_LSE = 11,   /* ARGMAX and LSE in one pass over the accumulators, for a greedy
+                                   decode with confidences and no logits write (fp32 GEMM only, no
+                                   qparams; it runs where ARGMAX runs at that shape).  C is
+                                   (rows, ldc) 8-byte slots, ldc >= 2 * ceil(N/32), 8-byte aligned:
+                                   for group g of 32 columns slot 2g is the ARGMAX key and slot
+                                   2g + 1 the LSE pair, or the neutral key 0 and pair {-inf, 0};
+                                   the 2 * ceil(N/32) slots of every row are all written with
+                                   plain stores, slots past them are not touched.  Columns >= N are
+                                   skipped for the key and count as -inf for the pair; a -inf bias
+                                   entry is allowed.  On the tile kernels each key is bitwise
+                                   ARGMAX's and each pair bitwise LSE's.  Consume with
+                                   vasr_ctc_collapse_keys_conf */
+    VASR_EPI_LSE = 9            /* (8 and 10 are unassigned and refused.)
                                    row log-sum-exp of acc + bias, no logits write (fp32 GEMM
                                    only, no qparams; it runs on the engine the plain epilogue
                                    gets at that shape, vasr_gemm_tile): C is (rows, ldc) 8-byte slots
@@ -602,6 +614,39 @@ int vasr_ctc_collapse_var(const int32_t* pred, int B, int L, const int32_t* fram
 int vasr_ctc_collapse_keys(const uint64_t* keys, int64_t ld, int slots, int B, int L, const int32_t* frames,
                            int blank, int collapse, int32_t* pred, int32_t* out_tokens, int32_t* out_len,
                            int32_t* out_start, int32_t* out_end, void* stream);
+
+/* Greedy decode with confidences.  The log-probability of frame (b, t)'s argmax
+ * k* is lp[b,t] = (z[k*] - Ms) - lse, {Ms, lse} the row statistics as vasr_lse_combine_f32 defines
+ * them.  For kept token j of utterance b, whose run is frames [start, end) as vasr_ctc_collapse
+ * reports them with collapse = 1: out_logp_sum[b*L + j] = the sum of lp over the run (added left to
+ * right), out_logp_min[b*L + j] = its minimum; the run length is end - start.  out_path_logp[b] = the
+ * sum of lp over the utterance's frames, blank ones included (the log-probability of the greedy
+ * path; 0.0 for no frames): lane l of one wave adds frames l, l + 64, ... in order, then a fixed tree
+ * over the 64 lanes.  Every value depends on the utterance's own frames alone: bitwise repeatable
+ * and independent of B and of the other utterances.  All float32.
+ *
+ * vasr_argmax_logp_f32: out_idx bitwise vasr_argmax_f32, out_logp[row] = lp from an fp32
+ * max-subtracted log-sum-exp of the row; any V >= 1, any alignment. */
+int vasr_argmax_logp_f32(const float* logits, int64_t ld, int rows, int V, int32_t* out_idx, float* out_logp,
+                         void* stream);
+/* Collapse (B, L) predictions with their lp: one workgroup per utterance.  out_tokens, out_len,
+ * out_start, out_end are bitwise those of vasr_ctc_collapse[_var] with collapse = 1 (all required here).
+ * frames: NULL (all L rows) or device int32[B], clamped to [0, L]; no row at or past the clamped
+ * count is read.  1 <= L <= 8192 (VASR_EINVAL otherwise); only the first out_len[b] entries of an
+ * output row are written. */
+int vasr_ctc_collapse_conf(const int32_t* pred, const float* logp, int B, int L, const int32_t* frames, int blank,
+                           int32_t* out_tokens, int32_t* out_len, int32_t* out_start, int32_t* out_end,
+                           float* out_logp_sum, float* out_logp_min, float* out_path_logp, void* stream);
+/* The same straight from a VASR_EPI_ARGMAX_LSE GEMM's slots (B * L rows of row stride ld, nslots =
+ * 2 * ceil(N/32) used: key, pair, key, pair, ...), in ONE launch: per row the keys fold as
+ * vasr_argmax_keys folds them and the pairs as vasr_lse_combine_f32 does, the maximum logit is read
+ * back out of the largest key's float bits, then the collapse above.  The per-frame values stay in
+ * LDS; pred / logp: NULL or device int32 / float [B * L] to also receive them (rows at or past an
+ * utterance's count are neither read nor written). */
+int vasr_ctc_collapse_keys_conf(const uint64_t* slots, int64_t ld, int nslots, int B, int L, const int32_t* frames,
+                                int blank, int32_t* pred, float* logp, int32_t* out_tokens, int32_t* out_len,
+                                int32_t* out_start, int32_t* out_end, float* out_logp_sum, float* out_logp_min,
+                                float* out_path_logp, void* stream);
 
 /* ------------------------------------------------------------------ CTC loss and forced alignment
  * Forward-only scoring of a KNOWN transcript (training.py:47-104: F.log_softmax + nn.CTCLoss as

@@ -762,19 +762,9 @@ __global__ __launch_bounds__(kCombineWaves* kWave) void lse_combine_kernel(const
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t r = (int64_t)blockIdx.x * kCombineWaves + (threadIdx.x >> 6);
     if (r >= M) return;
-    const float2* row = pairs + r * ld;
     // running (m, s) per lane over slots lane, lane + 64, ...; then the 64 lanes as row_lse does
-    float m = -INFINITY, s = 0.f;
-    for (int j = lane; j < slots; j += kWave) {
-        const float2 e = row[j];
-        const float mn = fmaxf(m, e.x);
-        const float ms = mn == -INFINITY ? 0.f : mn;
-        s = s * fast_exp(m - ms) + e.y * fast_exp(e.x - ms);
-        m = mn;
-    }
-    const float Mx = wave_max(m);
-    const float Ms = Mx == -INFINITY ? 0.f : Mx;
-    const float lse = logf(wave_sum(s * fast_exp(m - Ms)));
+    float Ms;
+    const float lse = lse_pairs_fold(pairs + r * ld, 1, slots, lane, Ms);
     if (lane == 0) reinterpret_cast<float2*>(stats)[r] = make_float2(Ms, lse);
 }
 

@@ -85,6 +85,29 @@ __device__ __forceinline__ unsigned long long max_u64_over_32_lanes(unsigned lon
     return o > k ? o : k;
 }
 
+// The second half of the LSE and ARGMAX_LSE epilogues: lane (r, h) combines half h of row r of the
+// wave's transposed {m, s} pairs (scr2: 32 rows of 33 entries), the maximum first, then one exp per
+// entry, and the halves meet across h.  One definition for both epilogues, with contraction off and
+// the fused multiply-adds written out: left to the compiler, the choice between a packed multiply
+// with separate adds and an FMA chain differed between instantiations by an ulp of S, and the two
+// epilogues' pairs are bitwise equal by contract (tests/test_greedy_conf_gpu.py).
+__device__ __forceinline__ void lse_row_pair(const float2* scr2, int r, int h, float& M, float& S) {
+#pragma clang fp contract(off)
+    float2 e[16];
+    M = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        e[j] = scr2[r * 33 + 16 * h + j];
+        M = fmaxf(M, e[j].x);
+    }
+    M = fmaxf(M, __shfl_xor(M, 32, 64));
+    const float Ms = M == -INFINITY ? 0.f : M;
+    S = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) S = __builtin_fmaf(e[j].y, fast_exp(e[j].x - Ms), S);
+    S += __shfl_xor(S, 32, 64);
+}
+
 // Accumulator element i of MFMA tile (tm, tn) of wave (wr, wc), lane (r, h) is
 // C[m0 + wr*32*TM + tm*32 + (i&3) + 8*(i>>2) + 4*h][n0 + wc*32*TN + tn*32 + r].
 //
@@ -255,20 +278,8 @@ __device__ __forceinline__ void epilogue_body(const GemmParams& p, const Tile& t
             }
             __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
             __builtin_amdgcn_wave_barrier();
-            // lane (r, h) combines half h of row r: the maximum first, then one exp per entry
-            float2 e[16];
-            float M = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                e[j] = scr2[r * 33 + 16 * h + j];
-                M = fmaxf(M, e[j].x);
-            }
-            M = fmaxf(M, __shfl_xor(M, 32, 64));
-            const float Ms = M == -INFINITY ? 0.f : M;
-            float S = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) S += e[j].y * fast_exp(e[j].x - Ms);
-            S += __shfl_xor(S, 32, 64);
+            float M, S;
+            lse_row_pair(scr2, r, h, M, S);
             __builtin_amdgcn_s_waitcnt(0xC07F);
             __builtin_amdgcn_wave_barrier();  // all reads done before the next tm overwrites scr
             const int row = m0 + wr * 32 * TM + tm * 32 + r;
@@ -277,6 +288,91 @@ __device__ __forceinline__ void epilogue_body(const GemmParams& p, const Tile& t
                 for (int sl = h; sl < TN; sl += 2)  // h = 0 writes the pair, h = 1 the neutral slots
                     if (!GUARD || (s0 + sl) * 32 < p.N)
                         pairs[(int64_t)row * p.ldc + s0 + sl] = sl == 0 ? make_float2(M, S) : make_float2(-INFINITY, 0.f);
+            }
+        }
+    } else if constexpr (EPI == VASR_EPI_ARGMAX_LSE) {
+        // both reductions in one pass over the accumulators: per row and group g of 32 columns,
+        // slot 2g of the row gets ARGMAX's key and slot 2g + 1 LSE's pair (the wave's first group
+        // carries them, its other groups the neutral key 0 and pair {-inf, 0}: every slot written,
+        // plain stores).  The key is computed exactly as ARGMAX computes it (columns past N
+        // skipped, acc alone without a bias) and the pair exactly as LSE does (acc + 0 without a
+        // bias, columns past N -inf), so each is bitwise the other epilogue's.  The two transposes
+        // go through the wave's one 32 x 33 x 8-byte scratch one after the other.
+        unsigned long long* __restrict__ keys =
+            reinterpret_cast<unsigned long long*>(p.C) + (int64_t)t.bz * p.stride_c;
+        float2* __restrict__ pairs = reinterpret_cast<float2*>(keys);
+        float2* scr2 = reinterpret_cast<float2*>(scr);
+        const int s0 = (n0 + wc * 32 * TN) / 32;
+        float bk[TN], bl[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            const int col = n0 + wc * 32 * TN + tn * 32 + r;
+            const bool ok = !GUARD || col < p.N;
+            bk[tn] = (p.bias && ok) ? p.bias[col] : 0.0f;
+            bl[tn] = ok ? (p.bias ? bk[tn] : 0.0f) : -INFINITY;
+        }
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                unsigned long long key = 0ull;
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    const int col = n0 + wc * 32 * TN + tn * 32 + r;
+                    if (GUARD && col >= p.N) continue;
+                    float v = acc[tm][tn][i];
+                    if (p.bias) v = v + bk[tn];
+                    const unsigned u = __float_as_uint(v);
+                    const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+                    const unsigned long long k = ((unsigned long long)ord << 32) | (0xFFFFFFFFu - (unsigned)col);
+                    key = k > key ? k : key;
+                }
+                // (the keys go through the scratch as float2 bit patterns, the type the pairs use after
+                // them: accesses of one type stay in program order for the compiler too)
+                scr2[((i & 3) + 8 * (i >> 2) + 4 * h) * 33 + r] = __builtin_bit_cast(float2, key);
+            }
+            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+            __builtin_amdgcn_wave_barrier();
+            unsigned long long key = 0ull;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const unsigned long long k = __builtin_bit_cast(unsigned long long, scr2[r * 33 + 16 * h + j]);
+                key = k > key ? k : key;
+            }
+            const unsigned long long ok_ = __shfl_xor(key, 32, 64);
+            key = ok_ > key ? ok_ : key;
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+            __builtin_amdgcn_wave_barrier();  // the keys are read before the pairs overwrite scr
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                float v[TN];
+                float m = -INFINITY;
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    v[tn] = acc[tm][tn][i] + bl[tn];
+                    m = fmaxf(m, v[tn]);
+                }
+                const float ms = m == -INFINITY ? 0.f : m;
+                float s = 0.f;
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) s += fast_exp(v[tn] - ms);
+                scr2[((i & 3) + 8 * (i >> 2) + 4 * h) * 33 + r] = make_float2(m, s);
+            }
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+            __builtin_amdgcn_wave_barrier();
+            float M, S;
+            lse_row_pair(scr2, r, h, M, S);
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+            __builtin_amdgcn_wave_barrier();  // all reads done before the next tm overwrites scr
+            const int row = m0 + wr * 32 * TM + tm * 32 + r;
+            if (!GUARD || row < p.M) {
+#pragma unroll
+                for (int sl = 0; sl < TN; ++sl) {  // h = 0 writes the group's key slot, h = 1 its pair slot
+                    if (GUARD && (s0 + sl) * 32 >= p.N) continue;
+                    const int64_t at = (int64_t)row * p.ldc + 2 * (s0 + sl);
+                    if (h == 0) keys[at] = sl == 0 ? key : 0ull;
+                    else pairs[at + 1] = sl == 0 ? make_float2(M, S) : make_float2(-INFINITY, 0.f);
+                }
             }
         }
     } else {
@@ -319,7 +415,7 @@ __device__ __forceinline__ void epilogue_body(const GemmParams& p, const Tile& t
 
 // scr: optional per-wave LDS scratch of 32 x 33 uint64 for the ARGMAX row reduction (the
 // staging LDS is free once the main loop is done); null selects the DPP reduction.  LSE needs it
-// (32 x 33 float pairs).
+// (32 x 33 float pairs), and so does ARGMAX_LSE (keys, then pairs, through the same scratch).
 template <int BM, int BN, int TM, int TN, int EPI>
 __device__ __forceinline__ void epilogue(const GemmParams& p, const Tile& t, floatx16 (&acc)[TM][TN], int wr,
                                          int wc, int r, int h, unsigned long long* scr = nullptr) {
@@ -350,8 +446,8 @@ inline int check_args(const vasr_gemm_args* a, const char* fn, GemmParams& p) {
                    "%s: K, lda, stride_a must be multiples of 4 (K=%d lda=%lld)", fn, a->K, (long long)a->lda);
     VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->A) & 15) == 0, "%s: A must be 16-byte aligned", fn);
     const int epi = a->epilogue;
-    VASR_CHECK_ARG((epi >= VASR_EPI_NONE && epi <= VASR_EPI_ARGMAX) || epi == VASR_EPI_LSE, "%s: unknown epilogue %d", fn,
-                   epi);
+    VASR_CHECK_ARG((epi >= VASR_EPI_NONE && epi <= VASR_EPI_ARGMAX) || epi == VASR_EPI_LSE || epi == VASR_EPI_ARGMAX_LSE,
+                   "%s: unknown epilogue %d", fn, epi);
     if (epi == VASR_EPI_ARGMAX)
         VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->C) & 7) == 0 && a->ldc >= (a->N + 31) / 32,
                        "%s: argmax keys must be 8-byte aligned with ldc >= ceil(N / 32) slots", fn);
@@ -359,6 +455,11 @@ inline int check_args(const vasr_gemm_args* a, const char* fn, GemmParams& p) {
         VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->C) & 7) == 0 && a->ldc >= (a->N + 31) / 32,
                        "%s: lse pairs must be 8-byte aligned with ldc >= ceil(N / 32) slots", fn);
         VASR_CHECK_ARG(a->qparams == nullptr, "%s: qparams not allowed with LSE", fn);
+    }
+    if (epi == VASR_EPI_ARGMAX_LSE) {
+        VASR_CHECK_ARG((reinterpret_cast<uintptr_t>(a->C) & 7) == 0 && a->ldc >= 2 * (int64_t)((a->N + 31) / 32),
+                       "%s: argmax+lse slots must be 8-byte aligned with ldc >= 2 * ceil(N / 32) slots", fn);
+        VASR_CHECK_ARG(a->qparams == nullptr, "%s: qparams not allowed with ARGMAX_LSE", fn);
     }
     const bool pair = epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION;
     if (pair)

@@ -516,6 +516,57 @@ __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buf
         }
         return;
     }
+    if constexpr (EPI == VASR_EPI_ARGMAX_LSE) {
+        // the chunk is the row's group n0 / 32: slot 2 * group gets the key exactly as ARGMAX above
+        // forms it, slot 2 * group + 1 the pair exactly as LSE above (gemm_common.h's layout; no
+        // qparams, the host refuses them); lane c4 == 0 stores both
+        const int slot = 2 * (n0 / 32);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int row = m0 + 8 * s + rl;
+            const float4 x = *reinterpret_cast<const float4*>(tile + (8 * s + rl) * 32 + c4);
+            const float xv[4] = {x.x, x.y, x.z, x.w};
+            unsigned long long key = 0ull;
+            float v[4];
+            float m = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float kvl = xv[e];
+                if (p.bias) kvl = kvl + bv[e];
+                const unsigned u = __float_as_uint(kvl);
+                const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+                const unsigned long long k =
+                    col0 + e < p.N ? ((unsigned long long)ord << 32) | (0xFFFFFFFFu - (unsigned)(col0 + e)) : 0ull;
+                key = k > key ? k : key;
+                v[e] = col0 + e < p.N ? xv[e] + bv[e] : -INFINITY;
+                m = fmaxf(m, v[e]);
+            }
+            unsigned long long o = gemm::dpp_u64<0xB1, 0xF>(key);
+            key = o > key ? o : key;
+            o = gemm::dpp_u64<0x4E, 0xF>(key);
+            key = o > key ? o : key;
+            o = gemm::dpp_u64<0x141, 0xF>(key);
+            key = o > key ? o : key;
+            m = fmaxf(m, dpp_f32<0xB1>(m));
+            m = fmaxf(m, dpp_f32<0x4E>(m));
+            m = fmaxf(m, dpp_f32<0x141>(m));
+            const float ms = m == -INFINITY ? 0.f : m;
+            float sum = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sum += fast_exp(v[e] - ms);
+            sum += dpp_f32<0xB1>(sum);
+            sum += dpp_f32<0x4E>(sum);
+            sum += dpp_f32<0x141>(sum);
+            const bool on = c4 == 0 && row < p.M;
+            const int off = on ? (row * (int)p.ldc + slot) * 8 : OOB16;
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            const u32x2 kv = {(unsigned)key, (unsigned)(key >> 32)};
+            const u32x2 pv = {__float_as_uint(m), __float_as_uint(sum)};
+            __builtin_amdgcn_raw_buffer_store_b64(kv, cbuf, off, 0, VASR_ROWS_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(pv, cbuf, on ? off + 8 : OOB16, 0, VASR_ROWS_STORE_AUX);
+        }
+        return;
+    }
     auto body = [&](auto SPc, auto Wc) {
         constexpr int SP = decltype(SPc)::value;
         constexpr bool WIDE = decltype(Wc)::value;
@@ -681,8 +732,9 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the tables are in LDS before B_0
         if (dma)
             for (int j = 0; j < DEPTH && j < nc; ++j) issue(j);
-        constexpr bool SLOTS = EPI == VASR_EPI_ARGMAX || EPI == VASR_EPI_LSE;  // C is 8-byte slots, one per chunk
-        const int c_bytes = (SLOTS ? 8 : 4) * ((p.M - 1) * (int)p.ldc + (SLOTS ? NT : p.N));
+        constexpr bool SLOTS = EPI == VASR_EPI_ARGMAX || EPI == VASR_EPI_LSE || EPI == VASR_EPI_ARGMAX_LSE;  // C is 8-byte slots, one per chunk
+        constexpr int PER = EPI == VASR_EPI_ARGMAX_LSE ? 2 : 1;                                            // (two: key and pair)
+        const int c_bytes = (SLOTS ? 8 : 4) * ((p.M - 1) * (int)p.ldc + (SLOTS ? PER * NT : p.N));
         const __amdgpu_buffer_rsrc_t cbuf = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, c_bytes, 0x00020000);
         auto epilogue = [&](int j) {  // chunk j's tiles of compute waves sw, sw + SWV, ...
             if (!stores) return;
@@ -779,7 +831,7 @@ int launch_roles(const GemmParams& p, int epi, hipStream_t s) {
     int groups, per;
     pick_groups(row_blocks, NT, &groups, &per);
     // 16-byte stores need every lane's 4 columns valid together and 16-byte aligned
-    const int wide = epi != VASR_EPI_ARGMAX && epi != VASR_EPI_LSE && p.N % 4 == 0 && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
+    const int wide = epi != VASR_EPI_ARGMAX && epi != VASR_EPI_LSE && epi != VASR_EPI_ARGMAX_LSE && p.N % 4 == 0 && p.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0;
     const dim3 grid(row_blocks * groups), block(64 * (CWV + MWV));
 #define VASR_R(E) hipLaunchKernelGGL((gemm_rows_roles_kernel<KS, E>), grid, block, 0, s, p, groups, per, wide)
     switch (epi) {
@@ -790,6 +842,7 @@ int launch_roles(const GemmParams& p, int epi, hipStream_t s) {
         case VASR_EPI_GELU_PE: VASR_R(VASR_EPI_GELU_PE); break;
         case VASR_EPI_ARGMAX: VASR_R(VASR_EPI_ARGMAX); break;
         case VASR_EPI_LSE: VASR_R(VASR_EPI_LSE); break;
+        case VASR_EPI_ARGMAX_LSE: VASR_R(VASR_EPI_ARGMAX_LSE); break;
         default: set_error("vasr_linear_x3_f32: rows engine: epilogue %d not supported", epi); return VASR_EINVAL;
     }
 #undef VASR_R
@@ -824,10 +877,12 @@ int launch_rows(const GemmParams& p, int epi, hipStream_t s) {
 // nothing: vasr_linear_x3_f32 and vasr_gemm_tile both ask it); false when the tile kernel should run.
 bool rows_x3_selected(int M, int N, int Kp, int64_t ldc, int batch, int epi) {
     if (batch != 1 || Kp > 192 || M <= 0 || epi == VASR_EPI_PAIR_POWER || epi == VASR_EPI_PAIR_FUSION) return false;
-    if (epi == VASR_EPI_LSE && !VASR_ROWS_ROLES) return false;  // only the wave-specialised kernel has that epilogue
+    // only the wave-specialised kernel has the log-sum-exp epilogues
+    if ((epi == VASR_EPI_LSE || epi == VASR_EPI_ARGMAX_LSE) && !VASR_ROWS_ROLES) return false;
     if (Kp != 128 && Kp != 192) return false;  // the W chunk stride is Kp / 16 k-steps
     // raw-buffer C addressing: the valid bytes must fit the 31-bit offsets
-    if ((int64_t)M * ldc * (epi == VASR_EPI_ARGMAX || epi == VASR_EPI_LSE ? 8 : 4) >= ((int64_t)1 << 31) - 64) return false;
+    const bool slots = epi == VASR_EPI_ARGMAX || epi == VASR_EPI_LSE || epi == VASR_EPI_ARGMAX_LSE;
+    if ((int64_t)M * ldc * (slots ? 8 : 4) >= ((int64_t)1 << 31) - 64) return false;
     const int engine = option(VASR_OPT_GEMM_ENGINE);  // 0 auto, 1 tiles, 2 rows
     if (engine == 1) return false;
     // auto: the rows engine where it measured faster (profiles/r03l: K = 192, N >= 512 -- the

@@ -331,8 +331,10 @@ __global__ __launch_bounds__(256, (x3_occ<WM, WN, TM, TN, RING, P>())) void gemm
     }
     // ARGMAX, LSE: each wave gets 32 x 33 uint64 of the (now idle) staging LDS, two waves per slot
     unsigned long long* scr = nullptr;
-    static_assert(EPI != VASR_EPI_LSE || STAGE >= 2 * 32 * 33 * 8, "the LSE epilogue reduces through LDS");
-    if constexpr ((EPI == VASR_EPI_ARGMAX || EPI == VASR_EPI_LSE) && STAGE >= 2 * 32 * 33 * 8)  // else: the DPP reduction
+    // (ARGMAX_LSE runs its two transposes one after the other through that one scratch)
+    constexpr bool LDS_EPI = EPI == VASR_EPI_LSE || EPI == VASR_EPI_ARGMAX_LSE;
+    static_assert(!LDS_EPI || STAGE >= 2 * 32 * 33 * 8, "the LSE epilogues reduce through LDS");
+    if constexpr ((EPI == VASR_EPI_ARGMAX || LDS_EPI) && STAGE >= 2 * 32 * 33 * 8)  // else: the DPP reduction
         scr = reinterpret_cast<unsigned long long*>(wave < 2 ? s0 : s1) + (wave & 1) * 32 * 33;
     epilogue<BM, BN, TM, TN, EPI>(p, t, acc, wr, wc, r, h, scr);
 }
@@ -361,6 +363,9 @@ int launch_cfg(const GemmParams& p, int batch, int epi, hipStream_t s) {
         case VASR_EPI_LSE:  // fp32 only: the split GEMM's three tiles
             if constexpr (P == 3) { VASR_L(VASR_EPI_LSE); break; }
             set_error("vasr_linear_bf16: the LSE epilogue is fp32 only"); return VASR_EINVAL;
+        case VASR_EPI_ARGMAX_LSE:
+            if constexpr (P == 3) { VASR_L(VASR_EPI_ARGMAX_LSE); break; }
+            set_error("vasr_linear_bf16: the ARGMAX_LSE epilogue is fp32 only"); return VASR_EINVAL;
         default: set_error("vasr_linear_x3_f32: unknown epilogue %d", epi); return VASR_EINVAL;
     }
 #undef VASR_L
@@ -559,14 +564,18 @@ VASR_API int vasr_gemm_tile(int M, int N, int K, int batch, int epilogue, int bf
     using namespace vasr;
     VASR_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 4 == 0 && batch >= 1, "vasr_gemm_tile: bad shape M=%d N=%d K=%d batch=%d",
                    M, N, K, batch);
-    VASR_CHECK_ARG((epilogue >= VASR_EPI_NONE && epilogue <= VASR_EPI_ARGMAX) || epilogue == VASR_EPI_LSE,
+    VASR_CHECK_ARG((epilogue >= VASR_EPI_NONE && epilogue <= VASR_EPI_ARGMAX) || epilogue == VASR_EPI_LSE ||
+                       epilogue == VASR_EPI_ARGMAX_LSE,
                    "vasr_gemm_tile: unknown epilogue %d", epilogue);
     VASR_CHECK_ARG(!(epilogue == VASR_EPI_LSE && bf16), "vasr_gemm_tile: the LSE epilogue is fp32 only");
+    VASR_CHECK_ARG(!(epilogue == VASR_EPI_ARGMAX_LSE && bf16), "vasr_gemm_tile: the ARGMAX_LSE epilogue is fp32 only");
     VASR_CHECK_ARG(bf16 == 0 || bf16 == 1, "vasr_gemm_tile: bf16 must be 0 or 1");
     const bool pair = epilogue == VASR_EPI_PAIR_POWER || epilogue == VASR_EPI_PAIR_FUSION;
     VASR_CHECK_ARG(!pair || N % 64 == 0, "vasr_gemm_tile: paired epilogue needs N %% 64 == 0");
-    // a dense C: ldc = N columns, or ceil(N / 32) 8-byte slots for ARGMAX / LSE
-    const int64_t ldc = epilogue == VASR_EPI_ARGMAX || epilogue == VASR_EPI_LSE ? (N + 31) / 32 : N;
+    // a dense C: ldc = N columns, or ceil(N / 32) 8-byte slots for ARGMAX / LSE (twice that for ARGMAX_LSE)
+    const int64_t ldc = epilogue == VASR_EPI_ARGMAX || epilogue == VASR_EPI_LSE ? (N + 31) / 32
+                        : epilogue == VASR_EPI_ARGMAX_LSE                        ? 2 * ((N + 31) / 32)
+                                                                                 : N;
     const int k = select_kernel(M, N, K, ldc, batch, epilogue, bf16 != 0);
     if (k == kRows) return 1;
     const TileCfg& c = kCfgs[k];

@@ -74,6 +74,38 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// fast_exp below; used by lse_pairs_fold
+__device__ __forceinline__ float fast_exp(float x);
+
+// The {m, s} pairs of one row of a VASR_EPI_LSE / VASR_EPI_ARGMAX_LSE GEMM, folded by one wave into
+// the row statistics: a running (m, s) per lane over pairs lane, lane + 64, ... (lse_pair_acc), then
+// the 64 lanes, the maximum first, then the rescaled sums (lse_pairs_finish: returns lse of the row
+// shifted by Ms, the row's maximum or 0 if every element is -inf, in every lane).  The one definition
+// vasr_lse_combine_f32 and the scored greedy decode share, so they agree bitwise (contraction off and
+// the one fused multiply-add written out: the compiler's choice may not differ between the kernels).
+__device__ __forceinline__ void lse_pair_acc(float& m, float& s, float2 e) {
+#pragma clang fp contract(off)
+    const float mn = fmaxf(m, e.x);
+    const float ms = mn == -INFINITY ? 0.f : mn;
+    s = __builtin_fmaf(s, fast_exp(m - ms), e.y * fast_exp(e.x - ms));
+    m = mn;
+}
+__device__ __forceinline__ float lse_pairs_finish(float m, float s, float& Ms) {
+#pragma clang fp contract(off)
+    float Mx = m;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) Mx = fmaxf(Mx, __shfl_xor(Mx, o, kWave));
+    Ms = Mx == -INFINITY ? 0.f : Mx;
+    return logf(wave_sum(s * fast_exp(m - Ms)));
+}
+// pair j of the row at row[j * step], `slots` of them
+__device__ __forceinline__ float lse_pairs_fold(const float2* __restrict__ row, int step, int slots, int lane,
+                                                float& Ms) {
+    float m = -INFINITY, s = 0.f;
+    for (int j = lane; j < slots; j += kWave) lse_pair_acc(m, s, row[(int64_t)j * step]);
+    return lse_pairs_finish(m, s, Ms);
+}
+
 // Exact (erf) GELU, nn.GELU() default.
 __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

@@ -3,7 +3,7 @@
 
 Same command line and outputs as the reference's scripts/transcribe.py:
 
-    python scripts/transcribe.py audio.wav --checkpoint model.pt [--timestamps] [--format json]
+    python scripts/transcribe.py audio.wav --checkpoint model.pt [--timestamps] [--confidence] [--format json]
     python scripts/transcribe.py --input-dir ./audio --output-dir ./out --checkpoint model.pt
 
 Files of equal length are transcribed together as one device batch (--batch-size).
@@ -35,6 +35,8 @@ def parse_args(argv=None):
     p.add_argument("--output", "-o", default=None, help="Output file path")
     p.add_argument("--format", choices=["text", "json"], default="text", help="Output format")
     p.add_argument("--timestamps", action="store_true", help="Include word-level timestamps")
+    p.add_argument("--confidence", action="store_true",
+                   help="Include a confidence per word and the greedy path's log-probability (implies --timestamps)")
     p.add_argument("--device", default="cuda", help="HIP device to run inference on")
     p.add_argument("--quiet", "-q", action="store_true", help="Suppress logging output")
     p.add_argument("--batch-size", type=int, default=16, help="Max equal-length files per device batch")
@@ -65,7 +67,7 @@ def main(argv=None) -> int:
             os.makedirs(args.output_dir, exist_ok=True)
         results = []
         for path, r in zip(files, transcribe_files(model, files, decoder, args.device, args.timestamps,
-                                                    args.batch_size)):
+                                                    args.batch_size, confidence=args.confidence)):
             if "error" in r:
                 logger.error(f"Error processing {path}: {r['error']}")
                 continue
@@ -90,7 +92,7 @@ def main(argv=None) -> int:
         logger.info(f"Processed {len(results)} files")
         return 0
 
-    r = transcribe_files(model, [args.audio], decoder, args.device, args.timestamps, 1)[0]
+    r = transcribe_files(model, [args.audio], decoder, args.device, args.timestamps, 1, confidence=args.confidence)[0]
     if "error" in r:
         logger.error(f"Error processing {args.audio}: {r['error']}")
         return 1

@@ -24,6 +24,7 @@ HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vasr.
 (EPI_NONE, EPI_GELU, EPI_SOFTPLUS_FROM, EPI_RESIDUAL, EPI_GELU_PE, EPI_PAIR_POWER, EPI_PAIR_FUSION,
  EPI_ARGMAX) = range(8)
 EPI_LSE = 9  # 8 is unassigned: refused as an unknown epilogue
+EPI_ARGMAX_LSE = 11  # 10 is unassigned too
 OPT_SCAN_LANES, OPT_SCAN_CHUNK, OPT_TAIL_ROWS, OPT_GEMM_ENGINE, OPT_TAIL_WAVES, OPT_SCAN_SPLIT, OPT_DW_ROWS = range(7)  # enum vasr_option
 
 c_i32, c_i64, c_f32, c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -127,6 +128,10 @@ _SIGNATURES = {
     "vasr_argmax_keys": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p], ctypes.c_int),
     "vasr_ctc_collapse_keys": ([c_p, c_i64] + [ctypes.c_int] * 3 + [c_p, ctypes.c_int, ctypes.c_int] + [c_p] * 6,
                                ctypes.c_int),
+    "vasr_argmax_logp_f32": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p], ctypes.c_int),
+    "vasr_ctc_collapse_conf": ([c_p, c_p, ctypes.c_int, ctypes.c_int, c_p, ctypes.c_int] + [c_p] * 8, ctypes.c_int),
+    "vasr_ctc_collapse_keys_conf": ([c_p, c_i64] + [ctypes.c_int] * 3 + [c_p, ctypes.c_int] + [c_p] * 10,
+                                    ctypes.c_int),
     "vasr_ctc_beam_search": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 5 + [c_p] * 5 + [c_p], ctypes.c_int),
     "vasr_ctc_beam_search_lm": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p, c_i64, ctypes.c_double]
                                 + [c_p] * 5 + [c_p], ctypes.c_int),

@@ -23,7 +23,8 @@ BLANK_TOKEN = 0
 # imported from here.
 __all__ = ["BLANK_TOKEN", "DecodingResult", "ctc_greedy_decode", "ctc_greedy_decode_with_timestamps",
            "ctc_beam_search", "ctc_forced_align", "BigramLM", "CTCDecoder", "create_default_vocabulary",
-           "greedy_token_ids"]
+           "greedy_token_ids", "ScoredDecoding", "ctc_greedy_decode_with_confidence", "token_confidences",
+           "AGGREGATIONS"]
 
 
 @dataclass
@@ -71,6 +72,72 @@ def ctc_greedy_decode_with_timestamps(logits: torch.Tensor,
         n = int(lens[b])
         out.append((toks[b, :n].tolist(), [(int(s), int(e)) for s, e in zip(st[b, :n], en[b, :n])]))
     return out
+
+
+@dataclass
+class ScoredDecoding:
+    """Greedy decoding of one utterance with confidences (not in the reference): the kept tokens,
+    their (start_frame, end_frame) spans, one confidence in (0, 1] per token, and `score`, the
+    log-probability of the greedy path (the sum over the utterance's frames, blank ones included,
+    of the log-softmax value at the argmax)."""
+
+    tokens: List[int]
+    timestamps: List[Tuple[int, int]]
+    confidences: List[float]
+    score: float
+
+
+AGGREGATIONS = ("mean", "min", "prod")
+
+
+def token_confidences(logp_sum, logp_min, run_lengths, aggregation: str = "mean") -> List[float]:
+    """Per-token confidences from the device's per-token values (host arithmetic, float64): the sum
+    and the minimum of the frame log-probabilities over a token's run and the run's length.
+    "mean": exp(sum / length), the geometric mean of the frame probabilities; "min": exp(min), the
+    weakest frame; "prod": exp(sum), the probability of the whole run."""
+    if aggregation not in AGGREGATIONS:
+        raise ValueError(f"aggregation must be one of {AGGREGATIONS}, got {aggregation!r}")
+    s = np.asarray(logp_sum, dtype=np.float64)
+    if aggregation == "mean":
+        v = s / np.maximum(np.asarray(run_lengths, dtype=np.float64), 1.0)
+    elif aggregation == "min":
+        v = np.asarray(logp_min, dtype=np.float64)
+    else:
+        v = s
+    return np.exp(v).tolist()
+
+
+def _scored_from_device(res, aggregation: str) -> List[ScoredDecoding]:
+    """ops.ctc_collapse_conf's device tuple -> one ScoredDecoding per utterance."""
+    if aggregation not in AGGREGATIONS:
+        raise ValueError(f"aggregation must be one of {AGGREGATIONS}, got {aggregation!r}")
+    toks, lens, st, en, lsum, lmin, path = (t.cpu().numpy() for t in res)
+    out = []
+    for b in range(toks.shape[0]):
+        n = int(lens[b])
+        spans = [(int(s), int(e)) for s, e in zip(st[b, :n], en[b, :n])]
+        conf = token_confidences(lsum[b, :n], lmin[b, :n], [e - s for s, e in spans], aggregation)
+        out.append(ScoredDecoding(toks[b, :n].tolist(), spans, conf, float(path[b])))
+    return out
+
+
+def ctc_greedy_decode_with_confidence(logits: torch.Tensor, blank_token: int = BLANK_TOKEN, input_lengths=None,
+                                      aggregation: str = "mean") -> List[ScoredDecoding]:
+    """ctc_greedy_decode_with_timestamps plus a confidence per token and the greedy path's
+    log-probability per utterance, all reduced on the device (vasr_argmax_logp_f32,
+    vasr_ctc_collapse_conf).  input_lengths (B,): row counts of a padded batch.  A model decodes
+    without logits through VELOCITYASR.greedy_scored instead."""
+    logits = _on_device(logits)
+    if logits.dim() != 3:
+        raise ValueError("ctc_greedy_decode_with_confidence: logits must be (B, L, V)")
+    if aggregation not in AGGREGATIONS:
+        raise ValueError(f"aggregation must be one of {AGGREGATIONS}, got {aggregation!r}")
+    if input_lengths is not None:
+        if not isinstance(input_lengths, torch.Tensor):
+            input_lengths = torch.tensor([int(n) for n in input_lengths], dtype=torch.int32)
+        input_lengths = input_lengths.to(device=logits.device, dtype=torch.int32).contiguous()
+    pred, lp = ops.argmax_logp(logits)
+    return _scored_from_device(ops.ctc_collapse_conf(pred, lp, blank_token, frames=input_lengths), aggregation)
 
 
 class BigramLM:
@@ -272,6 +339,13 @@ class CTCDecoder:
     def decode_greedy(self, logits: torch.Tensor, collapse_repeated: bool = True) -> List[str]:
         seqs = ctc_greedy_decode(logits, blank_token=self.blank_token, collapse_repeated=collapse_repeated)
         return [self._tokens_to_text(t) for t in seqs]
+
+    def decode_greedy_scored(self, logits: torch.Tensor, input_lengths=None) -> List[DecodingResult]:
+        """Greedy decoding as DecodingResults (extension): text, tokens, score = the greedy path's
+        log-probability, and the tokens' (start_frame, end_frame) spans."""
+        scored = ctc_greedy_decode_with_confidence(logits, blank_token=self.blank_token, input_lengths=input_lengths)
+        return [DecodingResult(text=self._tokens_to_text(r.tokens), tokens=r.tokens, score=r.score,
+                               timestamps=r.timestamps) for r in scored]
 
     def decode_beam_search(self, logits: torch.Tensor, beam_width: int = 10, return_all_beams: bool = False, *,
                            input_lengths=None, lm_scorer: Optional[Any] = None, lm_weight: float = 0.0):

@@ -156,6 +156,23 @@ class CTCOutputHead(nn.Module):
                                                ln=self._ln(normalized), out=out, frames=rows)
         return toks, lens
 
+    def greedy_scored(self, x: torch.Tensor, blank: int = 0, rows=None, normalized: bool = False):
+        """greedy(x) with time spans and confidences (extension): (tokens, lengths, start, end,
+        logp_sum, logp_min, path_logp) as ops.ctc_collapse_conf -- per kept token the sum and the
+        minimum over its run of frames of the log-softmax value at the argmax, per utterance the
+        sum over its frames (the log-probability of the greedy path).  A fusable() head never writes
+        the (B, L, V) logits: its GEMM leaves each row's argmax key and log-sum-exp pair
+        (VASR_EPI_ARGMAX_LSE) and one launch folds and collapses them.  A bf16 or QAT head goes
+        through forward() and ops.argmax_logp."""
+        B, L, D = x.shape
+        with torch.no_grad():
+            if self.fusable():
+                lin = self.proj[2]
+                return ops.gemm_ctc_greedy_conf(x.reshape(B * L, D), lin.weight, lin.bias, B, blank,
+                                                ln=self._ln(normalized), frames=rows)
+            pred, lp = ops.argmax_logp(self.forward(x, normalized=normalized))
+            return ops.ctc_collapse_conf(pred, lp, blank, frames=rows)
+
     def fusable(self) -> bool:
         """Whether the loss can run straight from the head's input (ops.ctc_head_emissions): a plain
         fp32 nn.Linear.  A bf16 or QAT head goes through its logits."""
@@ -314,6 +331,19 @@ class VELOCITYASR(nn.Module):
         with torch.no_grad():
             _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
             return self.ctc_head.greedy(x, blank, out=out, rows=rows, normalized=normalized)
+
+    def greedy_scored(self, mel_spectrogram: torch.Tensor, frames=None, blank: int = 0):
+        """greedy_token_ids with time spans and confidences, on the device: (tokens, lengths, start,
+        end, logp_sum, logp_min, path_logp) as CTCOutputHead.greedy_scored.  frames: per-utterance
+        mel frame counts of a zero-padded batch, as forward() takes them."""
+        if mel_spectrogram.device.type != "cuda":
+            _lib.require_device()
+            raise RuntimeError("velocity_asr (MI355X build): greedy_scored needs HIP tensors")
+        lengths = self._token_lengths(frames, mel_spectrogram.shape[1])
+        rows = None if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=mel_spectrogram.device)
+        with torch.no_grad():
+            _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
+            return self.ctc_head.greedy_scored(x, blank, rows=rows, normalized=normalized)
 
     def ctc_loss(self, mel_spectrogram: torch.Tensor, targets: torch.Tensor, input_lengths, target_lengths, *,
                  reduction: str = "mean", zero_infinity: bool = True, frames=None, blank: int = 0) -> torch.Tensor:

@@ -1418,3 +1418,109 @@ def ctc_grad_logits_stats(logits: torch.Tensor, stats: torch.Tensor, occ: torch.
                                                  int(blank), occ.data_ptr(), scale.data_ptr(), chain.data_ptr(),
                                                  chain.numel(), stream_of(logits)), "vasr_ctc_grad_logits_stats_f32")
     return logits
+
+
+# ---------------------------------------------------------------- greedy decode with confidences
+
+def gemm_argmax_lse(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, ln=None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The VASR_EPI_ARGMAX_LSE GEMM of a @ w.T + bias: (M, ld) int64 slots, 2 * ceil(N/32) used per row,
+    slot 2g the argmax key of columns 32g .. 32g + 31 and slot 2g + 1 their {m, s} float pair; the
+    (M, N) product is never written.  fp32 weights only.  ln = (weight, bias, eps): LayerNorm each
+    row of `a` first.  out: a caller's contiguous (M, ld >= 2 * ceil(N/32)) int64 buffer."""
+    a, (M, K, lda), (N, ldw) = _head_operands("gemm_argmax_lse", a, w, bias, ln)
+    nslots = 2 * ((N + 31) // 32)
+    if out is None:
+        out = torch.empty((M, nslots), device=a.device, dtype=torch.int64)  # every used slot is written
+    elif (out.device != a.device or out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != M
+          or out.shape[1] < nslots or not out.is_contiguous()):
+        raise ValueError(f"gemm_argmax_lse: out must be a contiguous int64 ({M}, >= {nslots}) tensor on {a.device}")
+    args = GemmArgs()
+    args.A, args.lda, args.stride_a = a.data_ptr(), lda, 0
+    args.W, args.ldw = w.data_ptr(), ldw
+    args.bias = ptr(bias)
+    args.C, args.ldc, args.stride_c = out.data_ptr(), out.shape[1], 0
+    args.batch, args.M, args.N, args.K = 1, M, N, K
+    args.epilogue = L.EPI_ARGMAX_LSE
+    ev = _t0("gemm")
+    _linear(args, w, stream_of(a))
+    _t1("gemm", ev, dict(M=M, N=N, K=K, batch=1))
+    return out
+
+
+def argmax_logp(logits: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(int32 argmax over the last dim as `argmax`, float32 log-softmax value at it)."""
+    _cuda_f32("argmax_logp.logits", logits)
+    V = logits.shape[-1]
+    x2 = logits.reshape(-1, V)
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    rows = x2.shape[0]
+    ld = x2.stride(0) if rows > 1 else V
+    idx = torch.empty(rows, device=logits.device, dtype=torch.int32)
+    lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    check(L.lib().vasr_argmax_logp_f32(x2.data_ptr(), ld, rows, V, idx.data_ptr(), lp.data_ptr(), stream_of(logits)),
+          "vasr_argmax_logp_f32")
+    return idx.view(logits.shape[:-1]), lp.view(logits.shape[:-1])
+
+
+def _conf_outputs(who: str, B: int, Lq: int, device, frames):
+    toks, lens, st, en, frames = _collapse_outputs(who, B, Lq, device, None, True, frames)
+    lsum = torch.empty((B, Lq), device=device, dtype=torch.float32)
+    lmin = torch.empty((B, Lq), device=device, dtype=torch.float32)
+    path = torch.empty((B,), device=device, dtype=torch.float32)
+    return toks, lens, st, en, lsum, lmin, path, frames
+
+
+def ctc_collapse_conf(pred: torch.Tensor, logp: torch.Tensor, blank: int = 0, frames: Optional[torch.Tensor] = None):
+    """Greedy CTC collapse of (B, L) int32 predictions with the float32 log-probability of each ->
+    (tokens, lengths, start, end, logp_sum, logp_min, path_logp): the first four as
+    ctc_collapse(timestamps=True); logp_sum / logp_min (B, L) the sum / minimum of logp over each
+    kept token's run of frames; path_logp (B,) the sum over the utterance's frames.  frames:
+    per-utterance row counts (int32 (B,)) of a padded batch."""
+    if pred.device.type != "cuda" or pred.dtype != torch.int32:
+        raise TypeError("ctc_collapse_conf: expected a cuda int32 pred")
+    _cuda_f32("ctc_collapse_conf.logp", logp)
+    if pred.dim() != 2 or logp.shape != pred.shape or logp.device != pred.device:
+        raise ValueError("ctc_collapse_conf: pred and logp must be (B, L) tensors on one device")
+    pred, logp = pred.contiguous(), logp.contiguous()
+    B, Lq = pred.shape
+    toks, lens, st, en, lsum, lmin, path, frames = _conf_outputs("ctc_collapse_conf", B, Lq, pred.device, frames)
+    check(L.lib().vasr_ctc_collapse_conf(pred.data_ptr(), logp.data_ptr(), B, Lq, ptr(frames), int(blank),
+                                         toks.data_ptr(), lens.data_ptr(), st.data_ptr(), en.data_ptr(),
+                                         lsum.data_ptr(), lmin.data_ptr(), path.data_ptr(), stream_of(pred)),
+          "vasr_ctc_collapse_conf")
+    return toks, lens, st, en, lsum, lmin, path
+
+
+def ctc_collapse_slots_conf(slots: torch.Tensor, nslots: int, B: int, blank: int = 0,
+                            frames: Optional[torch.Tensor] = None, per_frame: bool = False):
+    """ctc_collapse_conf straight from gemm_argmax_lse's slots ((B * L, ld) int64, `nslots` used) in one
+    launch (vasr_ctc_collapse_keys_conf).  per_frame: also return (pred, logp), the (B, L) per-frame
+    argmax and its log-probability (rows past an utterance's `frames` are not written)."""
+    if slots.device.type != "cuda" or slots.dtype != torch.int64 or slots.dim() != 2 or not slots.is_contiguous():
+        raise TypeError("ctc_collapse_slots_conf: expected a contiguous cuda int64 (rows, ld) tensor")
+    M, ld = slots.shape
+    if B <= 0 or M % B:
+        raise ValueError(f"ctc_collapse_slots_conf: {M} rows do not split into B={B} utterances")
+    Lq = M // B
+    toks, lens, st, en, lsum, lmin, path, frames = _conf_outputs("ctc_collapse_slots_conf", B, Lq, slots.device, frames)
+    pred = lp = None
+    if per_frame:
+        pred = torch.empty((B, Lq), device=slots.device, dtype=torch.int32)
+        lp = torch.empty((B, Lq), device=slots.device, dtype=torch.float32)
+    check(L.lib().vasr_ctc_collapse_keys_conf(slots.data_ptr(), ld, int(nslots), B, Lq, ptr(frames), int(blank),
+                                              ptr(pred), ptr(lp), toks.data_ptr(), lens.data_ptr(), st.data_ptr(),
+                                              en.data_ptr(), lsum.data_ptr(), lmin.data_ptr(), path.data_ptr(),
+                                              stream_of(slots)), "vasr_ctc_collapse_keys_conf")
+    res = (toks, lens, st, en, lsum, lmin, path)
+    return res + (pred, lp) if per_frame else res
+
+
+def gemm_ctc_greedy_conf(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], B: int, blank: int = 0, *,
+                         ln=None, frames: Optional[torch.Tensor] = None, per_frame: bool = False):
+    """Greedy CTC decode of B utterances (a: B * L rows) with confidences and without logits: the
+    VASR_EPI_ARGMAX_LSE GEMM, then one launch that folds its slots and collapses
+    (ctc_collapse_slots_conf).  Returns ctc_collapse_conf's tuple (plus (pred, logp) with per_frame)."""
+    slots = gemm_argmax_lse(a, w, bias, ln=ln)
+    return ctc_collapse_slots_conf(slots, 2 * ((w.shape[0] + 31) // 32), B, blank, frames, per_frame)

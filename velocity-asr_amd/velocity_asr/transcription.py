@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from .audio import HOP_LENGTH, N_FFT, SAMPLE_RATE, load_audio, mel_on_device, ragged_supported
-from .decode import CTCDecoder
+from .decode import CTCDecoder, _scored_from_device
 
 logger = logging.getLogger(__name__)
 
@@ -38,32 +38,43 @@ def frames_to_seconds(frame_idx: int, hop_length: int = HOP_LENGTH, sample_rate:
     return (frame_idx * 2 * hop_length) / sample_rate
 
 
-def group_words(tokens: Sequence[int], spans: Sequence[Tuple[int, int]], vocabulary: Sequence[str]) -> List[Dict]:
+def group_words(tokens: Sequence[int], spans: Sequence[Tuple[int, int]], vocabulary: Sequence[str],
+                confidences: Optional[Sequence[float]] = None) -> List[Dict]:
     """Word segmentation of a timed token list (reference scripts/transcribe.py:83-117).
 
     A word is a run of non-separator characters (" " and "▁" separate). Its start is the
     first character's start frame; its end is the end frame of the separator that closes
     it, or of the utterance's last token for the final word — the reference's convention.
+    confidences (extension): one value per token; each word then carries "confidence", the
+    minimum over its own characters' tokens (separators do not count).
     """
     words: List[Dict] = []
     chars: List[str] = []
+    confs: List[float] = []
     first: Optional[int] = None
+    if confidences is not None and len(confidences) != len(tokens):
+        raise ValueError(f"group_words: {len(confidences)} confidences for {len(tokens)} tokens")
 
     def flush(end_frame: int) -> None:
         text = "".join(chars).replace("▁", "")
         if text:
-            words.append({"word": text, "start": frames_to_seconds(first), "end": frames_to_seconds(end_frame)})
+            word = {"word": text, "start": frames_to_seconds(first), "end": frames_to_seconds(end_frame)}
+            if confidences is not None:
+                word["confidence"] = min(confs)
+            words.append(word)
 
-    for tok, (s, e) in zip(tokens, spans):
+    for k, (tok, (s, e)) in enumerate(zip(tokens, spans)):
         ch = vocabulary[tok] if 0 <= tok < len(vocabulary) else "<unk>"
         if ch in (" ", "▁"):
             if chars:
                 flush(e)
-                chars, first = [], None
+                chars, confs, first = [], [], None
         else:
             if first is None:
                 first = s
             chars.append(ch)
+            if confidences is not None:
+                confs.append(float(confidences[k]))
     if chars and spans:
         flush(spans[-1][1])
     return words
@@ -71,10 +82,11 @@ def group_words(tokens: Sequence[int], spans: Sequence[Tuple[int, int]], vocabul
 
 def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: bool,
                   beam_width: int = 1, lengths: Optional[List[int]] = None, lm=None,
-                  lm_weight: float = 0.0) -> List[Tuple[str, Optional[List[Dict]]]]:
+                  lm_weight: float = 0.0, confidence: bool = False) -> List[Tuple]:
     """(b, S) device audio -> [(text, words or None)] through the device pipeline.  lengths:
     per-clip sample counts when the clips were zero-padded to S.  lm / lm_weight: language model
-    for the beam search (decode.BigramLM runs on the device)."""
+    for the beam search (decode.BigramLM runs on the device).  confidence (greedy only):
+    [(text, words with "confidence", path log-probability)] from model.greedy_scored."""
     with torch.no_grad():
         mel = mel_on_device(audio, n_mels=model.config.mel_bins, lengths=lengths,
                             frame_pad=model.temporal_binding.conv_padding())
@@ -85,6 +97,14 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
             rows = None if frames is None else [model.get_output_length(f) for f in frames]
             return [(t, None) for t in decoder.decode_beam_search(logits, beam_width=beam_width, input_lengths=rows,
                                                                   lm_scorer=lm, lm_weight=lm_weight)]
+        if confidence:
+            # the head's GEMM leaves each frame's argmax and log-sum-exp (no logits in HBM either)
+            scored = _scored_from_device(model.greedy_scored(mel, frames=frames, blank=decoder.blank_token), "mean")
+            out = []
+            for r in scored:
+                words = group_words(r.tokens, r.timestamps, decoder.vocabulary, r.confidences)
+                out.append((" ".join(w["word"] for w in words), words, r.score))
+            return out
         # greedy: the CTC head's GEMM reduces each frame to its argmax (no logits in HBM)
         rows = None
         if frames is not None:
@@ -123,14 +143,21 @@ def _batches(items: List[Tuple[int, torch.Tensor]], batch_size: int, ragged: boo
 
 
 def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timestamps: bool = False,
-                     batch_size: int = 16, beam_width: int = 1, lm=None, lm_weight: float = 0.0) -> List[Dict]:
+                     batch_size: int = 16, beam_width: int = 1, lm=None, lm_weight: float = 0.0,
+                     confidence: bool = False) -> List[Dict]:
     """Transcribe audio files; returns one result dict per file in input order.  lm / lm_weight:
     language model for beam_width > 1 (a decode.BigramLM is fused on the device).
+    confidence (extension, greedy only; implies timestamps): each word also carries
+    "confidence" in (0, 1], the minimum over its tokens of the geometric mean of the token's frame
+    probabilities, and each result "score", the log-probability of the greedy path.
 
     A result is {"file", "duration", "transcription"} (+ "words" with timestamps), as the
     reference's transcribe_file returns; a file that fails gets {"file", "error"} instead,
     so callers can log it the way the reference's per-file try/except does.
     """
+    if confidence and beam_width > 1:
+        raise ValueError("transcribe_files: confidence is reported for greedy decoding (beam_width = 1)")
+    timestamps = timestamps or confidence
     paths = [str(p) for p in paths]
     results: List[Optional[Dict]] = [None] * len(paths)
     items: List[Tuple[int, torch.Tensor]] = []
@@ -155,11 +182,14 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
             for j, (_, a) in enumerate(chunk):
                 audio[j, :ns[j]] = a.to(torch.float32)
             decoded = _decode_batch(model, audio.to(dev), decoder, timestamps, beam_width,
-                                    lengths=None if min(ns) == S else ns, lm=lm, lm_weight=lm_weight)
-            for (i, _), n, (text, words) in zip(chunk, ns, decoded):
-                r = {"file": paths[i], "duration": n / SAMPLE_RATE, "transcription": text}
+                                    lengths=None if min(ns) == S else ns, lm=lm, lm_weight=lm_weight,
+                                    confidence=confidence)
+            for (i, _), n, dec in zip(chunk, ns, decoded):
+                r = {"file": paths[i], "duration": n / SAMPLE_RATE, "transcription": dec[0]}
                 if timestamps:
-                    r["words"] = words
+                    r["words"] = dec[1]
+                if confidence:
+                    r["score"] = dec[2]
                 results[i] = r
         except Exception as e:
             for i, _ in chunk:
