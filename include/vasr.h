@@ -415,6 +415,37 @@ int vasr_flac_decode(const uint8_t* data, int64_t n, float* out, int64_t out_cap
 int64_t vasr_resample_length(int64_t n, int orig_sr, int new_sr);
 int vasr_resample_f32(const float* x, int channels, int64_t n, int64_t ld_x, int orig_sr, int new_sr,
                       float* y, int64_t ld_y);
+/* The resampler's kernel, exported for the device path (host functions).
+ * vasr_resample_plan: the geometry after reducing the rates by their gcd: a frame of `orig`
+ *   inputs gives `nw` outputs, each through klen = 2 * width + orig taps.  VASR_EINVAL for rates
+ *   <= 0 and for tables over 2^24 taps (44101 -> 16000), as vasr_resample_f32.
+ * vasr_resample_taps_f32: the row-major (nw, klen) float32 table (built in float64, rounded once)
+ *   that vasr_resample_f32 applies; cap >= nw * klen floats. */
+int vasr_resample_plan(int orig_sr, int new_sr, int* orig, int* nw, int* width, int* klen);
+int vasr_resample_taps_f32(int orig_sr, int new_sr, float* taps, int64_t cap);
+
+/* ------------------------------------------------------------------ resampling (device)
+ * vasr_resample_mix_f32: channel downmix + sample-rate conversion of a zero-padded batch in one
+ * launch, bit-identical to a fp32 downmix followed by vasr_resample_f32.  Clip b, channel c,
+ * sample i is x[b*ld_clip + c*ld_chan + i] (1 <= C <= 8); samples (device, optional): clip b has
+ * samples[b] in [1, S_in] samples, all S_in when NULL.  taps (device): the vasr_resample_taps_f32
+ * table of the pair whose vasr_resample_plan gave (orig, nw, width).
+ *   m[i]    = (x_0[i] + ... + x_{C-1}[i]) / C in float32, ascending channels, 0 outside the clip
+ *   y[b][o] = (float) sum_{k ascending} (double)taps[o % nw][k] * (double)m[(o / nw)*orig - width + k]
+ *             for o < vasr_resample_length(samples[b]): one float64 chain per output, the host
+ *             resampler's order, so the float32 results are its results bit for bit;
+ *   y[b][o] = 0 up to S_out (>= the output count of S_in samples; ld_y >= S_out); nothing is
+ *             written at or past S_out, so mel_on_device(lengths=) reads y as its padded batch.
+ * orig == nw (equal rates) is a downmix-and-copy and reads no taps.  No allocation, no
+ * synchronisation, no host read: the launch can be captured in a graph.  Argument errors return
+ * VASR_EINVAL before any device call, as does a geometry whose input span does not fit in LDS
+ * (callers then resample on the host).
+ * vasr_resample_tile_outputs: consecutive outputs one workgroup produces for (orig, nw); 0 when
+ * the geometry is refused. */
+int vasr_resample_mix_f32(const float* x, int64_t ld_clip, int64_t ld_chan, int B, int C, int S_in,
+                          const int32_t* samples, const float* taps, int orig, int nw, int width,
+                          float* y, int64_t ld_y, int S_out, void* stream);
+int vasr_resample_tile_outputs(int orig, int nw);
 
 /* ------------------------------------------------------------------ mel front end
  * compute_mel_spectrogram (audio.py:65-143) is three launches:

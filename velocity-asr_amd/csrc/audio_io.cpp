@@ -465,33 +465,35 @@ VASR_API int64_t vasr_resample_length(int64_t n, int orig_sr, int new_sr) {
 }
 
 namespace {
-int resample_f32(const float* x, int channels, int64_t n, int64_t ld_x, int orig_sr, int new_sr, float* y, int64_t ld_y) {
+// Geometry of the orig_sr -> new_sr kernel after the gcd reduction: (nw, klen = 2 * width + orig)
+// taps.  Rates with a small gcd (44101 -> 16000) would need gigabytes of kernel: refused.
+int resample_geometry(const char* who, int orig_sr, int new_sr, int* orig, int* nw, int* width, int* klen) {
     using namespace vasr;
-    VASR_CHECK_ARG(x && y && channels > 0 && n > 0 && orig_sr > 0 && new_sr > 0 && ld_x >= n,
-                   "vasr_resample_f32: bad arguments");
+    VASR_CHECK_ARG(orig_sr > 0 && new_sr > 0, "%s: bad arguments", who);
     int64_t g = orig_sr, r = new_sr;
     while (r) {
         const int64_t t = g % r;
         g = r;
         r = t;
     }
-    const int orig = (int)(orig_sr / g), nw = (int)(new_sr / g);
-    const int64_t out_len = vasr_resample_length(n, orig_sr, new_sr);
-    VASR_CHECK_ARG(ld_y >= out_len, "vasr_resample_f32: ld_y %lld < %lld outputs", (long long)ld_y, (long long)out_len);
-    if (orig == nw) {
-        for (int c = 0; c < channels; ++c) std::memcpy(y + c * ld_y, x + c * ld_x, sizeof(float) * n);
-        return VASR_OK;
-    }
+    *orig = (int)(orig_sr / g);
+    *nw = (int)(new_sr / g);
+    const double lpw = 6.0, rolloff = 0.99;
+    const double base = (double)(*orig < *nw ? *orig : *nw) * rolloff;
+    const int64_t w = (int64_t)std::ceil(lpw * *orig / base);
+    const int64_t kl = 2 * w + *orig;
+    VASR_CHECK_ARG((int64_t)*nw * kl <= ((int64_t)1 << 24), "%s: %d -> %d Hz needs a %lld-tap kernel (limit 2^24)", who,
+                   orig_sr, new_sr, (long long)*nw * kl);
+    *width = (int)w;
+    *klen = (int)kl;
+    return VASR_OK;
+}
+
+// The (nw, klen) taps, row-major: built in float64 and rounded to float32.  The one table the host
+// resampler and the device kernel (vasr_resample_taps_f32 exports it) both apply.
+void resample_taps(int orig, int nw, int width, int klen, float* kern) {
     const double lpw = 6.0, rolloff = 0.99;
     const double base = (double)(orig < nw ? orig : nw) * rolloff;
-    const int width = (int)std::ceil(lpw * orig / base);
-    const int klen = 2 * width + orig;
-    // (new, 2 * width + orig) taps after the gcd reduction: rates with a small gcd (44101 -> 16000)
-    // would need gigabytes of kernel
-    VASR_CHECK_ARG((int64_t)nw * klen <= ((int64_t)1 << 24),
-                   "vasr_resample_f32: %d -> %d Hz needs a %lld-tap kernel (limit 2^24)", orig_sr, new_sr,
-                   (long long)nw * klen);
-    std::vector<float> kern((size_t)nw * klen);
     const double pi = 3.14159265358979323846;
     for (int j = 0; j < nw; ++j) {
         for (int k = 0; k < klen; ++k) {
@@ -505,6 +507,22 @@ int resample_f32(const float* x, int channels, int64_t n, int64_t ld_x, int orig
             kern[(size_t)j * klen + k] = (float)(s * (window * (base / orig)));
         }
     }
+}
+
+int resample_f32(const float* x, int channels, int64_t n, int64_t ld_x, int orig_sr, int new_sr, float* y, int64_t ld_y) {
+    using namespace vasr;
+    VASR_CHECK_ARG(x && y && channels > 0 && n > 0 && orig_sr > 0 && new_sr > 0 && ld_x >= n,
+                   "vasr_resample_f32: bad arguments");
+    const int64_t out_len = vasr_resample_length(n, orig_sr, new_sr);
+    VASR_CHECK_ARG(ld_y >= out_len, "vasr_resample_f32: ld_y %lld < %lld outputs", (long long)ld_y, (long long)out_len);
+    if (orig_sr == new_sr) {
+        for (int c = 0; c < channels; ++c) std::memcpy(y + c * ld_y, x + c * ld_x, sizeof(float) * n);
+        return VASR_OK;
+    }
+    int orig, nw, width, klen;
+    if (int rc = resample_geometry("vasr_resample_f32", orig_sr, new_sr, &orig, &nw, &width, &klen)) return rc;
+    std::vector<float> kern((size_t)nw * klen);
+    resample_taps(orig, nw, width, klen, kern.data());
     for (int c = 0; c < channels; ++c) {
         const float* xc = x + c * ld_x;
         float* yc = y + c * ld_y;
@@ -523,6 +541,23 @@ int resample_f32(const float* x, int channels, int64_t n, int64_t ld_x, int orig
     return VASR_OK;
 }
 }  // namespace
+
+// The gcd-reduced geometry of a rate pair: orig inputs per frame, nw outputs per frame, the
+// filter's half width in inputs and klen = 2 * width + orig taps per output phase.
+VASR_API int vasr_resample_plan(int orig_sr, int new_sr, int* orig, int* nw, int* width, int* klen) {
+    VASR_CHECK_ARG(orig && nw && width && klen, "vasr_resample_plan: null argument");
+    return resample_geometry("vasr_resample_plan", orig_sr, new_sr, orig, nw, width, klen);
+}
+
+// The (nw, klen) row-major tap table vasr_resample_f32 applies (cap >= nw * klen floats).
+VASR_API int vasr_resample_taps_f32(int orig_sr, int new_sr, float* taps, int64_t cap) {
+    int orig, nw, width, klen;
+    if (int rc = resample_geometry("vasr_resample_taps_f32", orig_sr, new_sr, &orig, &nw, &width, &klen)) return rc;
+    VASR_CHECK_ARG(taps && cap >= (int64_t)nw * klen, "vasr_resample_taps_f32: table of %lld floats, %lld needed",
+                   (long long)cap, (long long)nw * klen);
+    resample_taps(orig, nw, width, klen, taps);
+    return VASR_OK;
+}
 
 VASR_API int vasr_resample_f32(const float* x, int channels, int64_t n, int64_t ld_x, int orig_sr, int new_sr, float* y,
                                int64_t ld_y) {

@@ -100,6 +100,11 @@ _SIGNATURES = {
     "vasr_flac_decode": ([c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p], ctypes.c_int),
     "vasr_resample_length": ([c_i64, ctypes.c_int, ctypes.c_int], c_i64),
     "vasr_resample_f32": ([c_p, ctypes.c_int, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_i64], ctypes.c_int),
+    "vasr_resample_plan": ([ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p], ctypes.c_int),
+    "vasr_resample_taps_f32": ([ctypes.c_int, ctypes.c_int, c_p, c_i64], ctypes.c_int),
+    "vasr_resample_mix_f32": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 3 + [c_p, c_p] + [ctypes.c_int] * 3
+                              + [c_p, c_i64, ctypes.c_int, c_p], ctypes.c_int),
+    "vasr_resample_tile_outputs": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
     "vasr_reflect_pad_f32": ([c_p, c_i64, c_p, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p], ctypes.c_int),
     "vasr_mel_log_norm_f32": ([c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p],
                               ctypes.c_int),

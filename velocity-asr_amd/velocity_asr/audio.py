@@ -120,11 +120,101 @@ def _read_flac(path: str) -> Tuple[torch.Tensor, int]:
     return torch.from_numpy(out), sr.value
 
 
+class _ResampleTable:
+    """Per (orig_freq, new_freq, device): the gcd-reduced geometry and, for a HIP device the kernel
+    serves, the host resampler's (nw, klen) float32 tap table uploaded once."""
+
+    def __init__(self, orig_freq: int, new_freq: int, device: Optional[torch.device]):
+        import ctypes
+        lib = _lib.lib()
+        g = [ctypes.c_int() for _ in range(4)]
+        _lib.check(lib.vasr_resample_plan(int(orig_freq), int(new_freq), *[ctypes.addressof(v) for v in g]),
+                   "vasr_resample_plan")
+        self.orig, self.nw, self.width, self.klen = (v.value for v in g)
+        # 0: the input span of one tile does not fit in LDS; such pairs are resampled on the host
+        self.tile_outputs = int(lib.vasr_resample_tile_outputs(self.orig, self.nw))
+        self.taps = None
+        if device is not None and self.tile_outputs and self.orig != self.nw:
+            t = np.empty((self.nw, self.klen), np.float32)
+            _lib.check(lib.vasr_resample_taps_f32(int(orig_freq), int(new_freq), t.ctypes.data, t.size),
+                       "vasr_resample_taps_f32")
+            self.taps = torch.from_numpy(t).to(device)
+
+
+_RESAMPLE_TABLES: Dict[tuple, _ResampleTable] = {}
+
+
+def _resample_table(orig_freq: int, new_freq: int, device: Optional[torch.device]) -> _ResampleTable:
+    key = (int(orig_freq), int(new_freq), None if device is None else str(device))
+    t = _RESAMPLE_TABLES.get(key)
+    if t is None:
+        t = _RESAMPLE_TABLES[key] = _ResampleTable(orig_freq, new_freq, device)
+    return t
+
+
+def device_resample_supported(orig_freq: int, new_freq: int) -> bool:
+    """Whether resample_on_device runs orig_freq -> new_freq in the HIP kernel: the pair has a tap
+    table (vasr_resample_plan accepts it) whose tile fits in LDS.  Other pairs go to the host."""
+    try:
+        return _resample_table(orig_freq, new_freq, None).tile_outputs > 0
+    except RuntimeError:
+        return False
+
+
+def resample_on_device(x: torch.Tensor, orig_freq: int, new_freq: int, lengths=None):
+    """Batched sample-rate conversion on the MI355X (extension): x (B, S) mono or (B, C, S), a
+    float32 HIP tensor of clips zero-padded to S -> (y (B, S_out), out_lengths).
+
+    Channels are averaged in float32 (ascending sum, then / C; C <= 8) and the host resampler's
+    float32 taps are applied in its own order with one float64 chain per output, so row b's first
+    out_lengths[b] values are bit for bit resample() of the downmixed clip alone; the rest of the
+    row is 0, which is the padded batch mel_on_device(lengths=out_lengths) reads.  lengths:
+    per-clip sample counts in [1, S] (all S when None).  One launch, nothing returns to the host.
+    A pair the kernel refuses (its input span does not fit in LDS) is resampled clip by clip on
+    the host and uploaded."""
+    if x.device.type != "cuda":
+        raise RuntimeError(f"resample_on_device: tensor is on {x.device}; pass a HIP tensor (resample() takes host ones)")
+    if x.dim() not in (2, 3) or x.shape[0] < 1 or x.shape[-1] < 1:
+        raise ValueError(f"resample_on_device: expected (B, S) or (B, C, S) with B, S >= 1, got {tuple(x.shape)}")
+    B, S = x.shape[0], x.shape[-1]
+    if lengths is None:
+        lengths = [S] * B
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != B or not all(1 <= v <= S for v in lengths):
+        raise ValueError(f"resample_on_device: lengths must be {B} sample counts in [1, {S}], got {lengths}")
+    lib = _lib.lib()
+    out_lengths = [int(lib.vasr_resample_length(v, int(orig_freq), int(new_freq))) for v in lengths]
+    tb = _resample_table(orig_freq, new_freq, x.device)
+    x = x.to(torch.float32)
+    if not tb.tile_outputs:
+        xh = x.cpu().reshape(B, -1, S)
+        y = torch.zeros((B, int(lib.vasr_resample_length(S, int(orig_freq), int(new_freq)))), dtype=torch.float32)
+        for b in range(B):
+            m = xh[b, 0, :lengths[b]].clone()
+            for c in range(1, xh.shape[1]):
+                m += xh[b, c, :lengths[b]]
+            y[b, :out_lengths[b]] = resample(m / xh.shape[1], orig_freq, new_freq)
+        return y.to(x.device), out_lengths
+    samples = None
+    if min(lengths) < S:
+        samples = torch.tensor(lengths, dtype=torch.int32).to(x.device)
+    return ops.resample_mix(x, tb.taps, tb.orig, tb.nw, tb.width, samples=samples), out_lengths
+
+
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
     """torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults (sinc_interp_hann,
-    lowpass_filter_width 6, rolloff 0.99) on a host (..., samples) float32 waveform, by the
-    library's host resampler (vasr_resample_f32).  Equality with torchaudio is unpinned
+    lowpass_filter_width 6, rolloff 0.99) on a (..., samples) float32 waveform.  A host tensor goes
+    through the library's host resampler (vasr_resample_f32) and returns a host tensor; a HIP
+    tensor goes through the device kernel (resample_on_device: the same taps in the same order, so
+    the same bits) and returns a HIP tensor.  Equality with torchaudio is unpinned
     (torchaudio is not installed here): same kernel formula, float64 accumulation."""
+    if waveform.device.type == "cuda":
+        lead, n = waveform.shape[:-1], waveform.shape[-1]
+        if n == 0 or waveform.numel() == 0:
+            m = int(_lib.lib().vasr_resample_length(n, int(orig_freq), int(new_freq)))
+            return torch.empty((*lead, m), device=waveform.device, dtype=torch.float32)
+        y, _ = resample_on_device(waveform.detach().reshape(-1, n), orig_freq, new_freq)
+        return y.reshape(*lead, y.shape[-1])
     x = np.ascontiguousarray(waveform.detach().cpu().numpy(), dtype=np.float32)
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
@@ -138,28 +228,68 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Ten
     return torch.from_numpy(y.reshape(*lead, m))
 
 
-def load_audio(path: str, sample_rate: int = SAMPLE_RATE, mono: bool = True) -> torch.Tensor:
+def read_audio(path: str) -> Tuple[torch.Tensor, int]:
+    """Decode a file without torchaudio: ((channels, samples) float32 host waveform, sample rate)
+    at the file's own rate.  WAV by the standard library, FLAC (LibriSpeech's format) by the
+    library's host decoder."""
+    low = str(path).lower()
+    if low.endswith(".wav"):
+        return _read_wav(path)
+    if low.endswith(".flac"):
+        return _read_flac(path)
+    raise ImportError("torchaudio is required for audio formats other than WAV and FLAC. "
+                      "Install with: pip install torchaudio")
+
+
+# torch's mean over channels equals the kernel's ascending sum / C bit for bit up to here; wider
+# files are averaged by torch on the host first, as the host path does
+_FUSED_DOWNMIX_CHANNELS = 4
+
+
+def _to_device_rate(waveform: torch.Tensor, sr: int, sample_rate: int, mono: bool, device) -> torch.Tensor:
+    """load_audio's downmix + resample steps on the device: the native-rate (C, n) host channels are
+    uploaded and converted there; bit for bit the host steps' result."""
+    dev = torch.device(device)
+    C, n = waveform.shape
+    if n == 0 or not (sr == sample_rate or device_resample_supported(sr, sample_rate)):
+        return _to_host_rate(waveform, sr, sample_rate, mono).to(dev)
+    if mono and C > _FUSED_DOWNMIX_CHANNELS:
+        waveform = waveform.mean(dim=0, keepdim=True)
+    x = waveform.to(device=dev, dtype=torch.float32)
+    if mono:
+        if x.size(0) == 1 and sr == sample_rate:
+            return x.squeeze(0)
+        return resample_on_device(x.unsqueeze(0), sr, sample_rate)[0].squeeze(0)  # one clip of C channels
+    return x if sr == sample_rate else resample_on_device(x, sr, sample_rate)[0]  # C mono clips
+
+
+def load_audio(path: str, sample_rate: int = SAMPLE_RATE, mono: bool = True, device=None) -> torch.Tensor:
     """Load audio and resample (reference audio.py:22-62).
 
     Uses torchaudio when it is installed (same as the reference); otherwise reads WAV with the
-    standard library and FLAC (LibriSpeech's format) with the library's host decoder, and
-    resamples with the host resampler that follows torchaudio's Resample defaults.  Returns
+    standard library and FLAC (LibriSpeech's format) with the library's host decoder (read_audio),
+    and resamples with the host resampler that follows torchaudio's Resample defaults.  Returns
     (samples,) for mono or (channels, samples), float32 on the host like the reference.
+
+    device (extension): decode on the host, upload the channels at the file's own rate, downmix and
+    resample there (resample_on_device) and return a tensor on that device, equal bit for bit to
+    the host result of the library's resampler.
     """
     try:
         import torchaudio
         waveform, sr = torchaudio.load(path)
         resampler = lambda w, a, b: torchaudio.transforms.Resample(a, b)(w)  # noqa: E731
     except ImportError:
-        low = path.lower()
-        if low.endswith(".wav"):
-            waveform, sr = _read_wav(path)
-        elif low.endswith(".flac"):
-            waveform, sr = _read_flac(path)
-        else:
-            raise ImportError("torchaudio is required for audio formats other than WAV and FLAC. "
-                              "Install with: pip install torchaudio")
+        waveform, sr = read_audio(path)
         resampler = resample
+    if device is not None:
+        return _to_device_rate(waveform, sr, sample_rate, mono, device)
+    return _to_host_rate(waveform, sr, sample_rate, mono, resampler)
+
+
+def _to_host_rate(waveform: torch.Tensor, sr: int, sample_rate: int = SAMPLE_RATE, mono: bool = True,
+                  resampler=resample) -> torch.Tensor:
+    """load_audio's steps after decoding, on the host (reference audio.py:50-60)."""
     if mono and waveform.size(0) > 1:
         waveform = waveform.mean(dim=0, keepdim=True)
     if sr != sample_rate:

@@ -832,6 +832,40 @@ def stft_power_400(audio: torch.Tensor, window: torch.Tensor, samples: Optional[
     return power
 
 
+def resample_mix(x: torch.Tensor, taps: Optional[torch.Tensor], orig: int, nw: int, width: int,
+                 samples: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Channel downmix + sample-rate conversion in one launch (vasr_resample_mix_f32).
+
+    x (B, C, S_in) or (B, S_in) float32 with unit stride along samples (clip and channel strides
+    are passed on, so views are read in place) -> (B, S_out), S_out = ceil(nw * S_in / orig).
+    taps: the (nw, 2 * width + orig) table of vasr_resample_taps_f32 on x's device; (orig, nw,
+    width) from vasr_resample_plan.  samples: per-clip sample counts (int32 (B,), each in
+    [1, S_in]) of a zero-padded batch; row b then holds the clip's own outputs followed by zeros."""
+    _cuda_f32("resample_mix.x", x)
+    if x.dim() == 2:
+        x = x.unsqueeze(1)
+    if x.dim() != 3 or x.shape[0] < 1 or x.shape[2] < 1:
+        raise ValueError(f"resample_mix: expected (B, C, S) or (B, S) with B, S >= 1, got {tuple(x.shape)}")
+    B, C, S_in = x.shape
+    # the stride of a dimension of size 1 is arbitrary (unsqueeze) and never used: pass S_in for it
+    ld_clip = x.stride(0) if B > 1 else S_in
+    ld_chan = x.stride(1) if C > 1 else S_in
+    if (S_in > 1 and x.stride(2) != 1) or ld_clip < S_in or ld_chan < S_in:
+        x = x.contiguous()
+        ld_clip, ld_chan = C * S_in, S_in
+    if orig != nw:
+        _cuda_f32("resample_mix.taps", taps)
+        if taps.device != x.device or not taps.is_contiguous() or taps.numel() != nw * (2 * width + orig):
+            raise ValueError(f"resample_mix: taps must be a contiguous ({nw}, {2 * width + orig}) table on {x.device}")
+    samples = _lens("resample_mix.samples", samples, B, x.device)
+    S_out = (nw * S_in + orig - 1) // orig
+    y = torch.empty((B, S_out), device=x.device, dtype=torch.float32)
+    check(L.lib().vasr_resample_mix_f32(x.data_ptr(), ld_clip, ld_chan, B, C, S_in, ptr(samples), ptr(taps),
+                                        orig, nw, width, y.data_ptr(), S_out, S_out, stream_of(x)),
+          "vasr_resample_mix_f32")
+    return y
+
+
 def mel_log_norm(power: torch.Tensor, ld_power: int, stride_power: int, fb_csr, B: int, F: int, n_mels: int,
                  normalize: bool, frames: Optional[torch.Tensor] = None, frame_pad: int = 0) -> torch.Tensor:
     """frames: per-utterance frame counts (int32 (B,), each <= F); frames past them are 0.

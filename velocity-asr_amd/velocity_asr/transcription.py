@@ -9,18 +9,23 @@ length (pipeline.audio_to_token_ids(..., lengths=)): the mel statistics, pooling
 attention keys and the collapse follow each clip's length and the SSM stacks are causal, so
 the output for a file is the one the reference's per-file loop produces.  Where the front end
 has no per-length kernels (VASR_STFT=gemm, n_mels > 85) batches hold clips of one length.
+Files that are not at 16 kHz are downmixed and resampled on the device as well (grouped by rate
+and channel count, audio.resample_on_device: the host resampler's values bit for bit) and their
+16 kHz samples stay there; VASR_DEVICE_RESAMPLE=0 or an installed torchaudio keeps the host path.
 """
 
 from __future__ import annotations
 
 import logging
+import os
 from pathlib import Path
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
-from .audio import HOP_LENGTH, N_FFT, SAMPLE_RATE, load_audio, mel_on_device, ragged_supported
+from . import _lib, ops
+from .audio import (HOP_LENGTH, N_FFT, SAMPLE_RATE, _FUSED_DOWNMIX_CHANNELS, _to_host_rate, device_resample_supported,
+                    load_audio, mel_on_device, ragged_supported, read_audio, resample_on_device)
 from .decode import CTCDecoder, _scored_from_device
 
 logger = logging.getLogger(__name__)
@@ -142,6 +147,33 @@ def _batches(items: List[Tuple[int, torch.Tensor]], batch_size: int, ragged: boo
         k = end
 
 
+def _device_resample_enabled() -> bool:
+    """Files that are not at 16 kHz are resampled on the device when the library's own resampler
+    is the one in use (torchaudio absent) and VASR_DEVICE_RESAMPLE is not "0" (read per call)."""
+    if os.environ.get("VASR_DEVICE_RESAMPLE", "1") == "0":
+        return False
+    try:
+        import torchaudio  # noqa: F401
+        return False
+    except ImportError:
+        return True
+
+
+def _resample_group(clips: List[torch.Tensor], sr: int, dev: torch.device) -> List[torch.Tensor]:
+    """Host (C, n_i) clips of one rate and channel count -> their mono 16 kHz samples, one 1-D
+    device tensor each: zero-padded to the longest, uploaded at their own rate, downmixed and
+    resampled in one launch (resample_on_device).  More than _FUSED_DOWNMIX_CHANNELS channels are
+    averaged by torch on the host first, as load_audio does."""
+    if clips[0].size(0) > _FUSED_DOWNMIX_CHANNELS:
+        clips = [w.mean(dim=0, keepdim=True) for w in clips]
+    ns = [w.size(1) for w in clips]
+    x = torch.zeros((len(clips), clips[0].size(0), max(ns)), dtype=torch.float32)
+    for j, w in enumerate(clips):
+        x[j, :, :ns[j]] = w
+    y, outs = resample_on_device(x.to(dev), sr, SAMPLE_RATE, lengths=ns)
+    return [y[j, :m] for j, m in enumerate(outs)]
+
+
 def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timestamps: bool = False,
                      batch_size: int = 16, beam_width: int = 1, lm=None, lm_weight: float = 0.0,
                      confidence: bool = False) -> List[Dict]:
@@ -161,24 +193,53 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
     paths = [str(p) for p in paths]
     results: List[Optional[Dict]] = [None] * len(paths)
     items: List[Tuple[int, torch.Tensor]] = []
+    dev = torch.device(device)
+    on_device = _device_resample_enabled()
+    native: Dict[Tuple[int, int], List[Tuple[int, torch.Tensor]]] = {}  # (rate, channels) -> clips to resample
+
+    def check_length(n: int) -> None:
+        if n < 2:
+            raise ValueError(f"expected a mono clip of at least 2 samples, got shape {(n,)}")
+        if n <= N_FFT // 2:  # the reference's reflect padding rejects it too
+            raise RuntimeError(f"compute_mel_spectrogram: reflect padding of {N_FFT // 2} needs more than "
+                               f"{N_FFT // 2} samples, got {n}")
+
     for i, p in enumerate(paths):
         try:
-            a = load_audio(p)
-            if a.dim() != 1 or a.numel() < 2:
+            if on_device:
+                w, sr = read_audio(p)
+                if sr != SAMPLE_RATE and device_resample_supported(sr, SAMPLE_RATE):
+                    # the length the resampler will give decides, before anything is uploaded
+                    check_length(int(_lib.lib().vasr_resample_length(w.size(1), sr, SAMPLE_RATE)))
+                    native.setdefault((sr, w.size(0)), []).append((i, w))
+                    continue
+                a = _to_host_rate(w, sr)
+            else:
+                a = load_audio(p)
+            if a.dim() != 1:
                 raise ValueError(f"expected a mono clip of at least 2 samples, got shape {tuple(a.shape)}")
-            if a.numel() <= N_FFT // 2:  # the reference's reflect padding rejects it too
-                raise RuntimeError(f"compute_mel_spectrogram: reflect padding of {N_FFT // 2} needs more than "
-                                   f"{N_FFT // 2} samples, got {a.numel()}")
+            check_length(a.numel())
             items.append((i, a))
         except Exception as e:  # reported per file, like the reference's loop
             results[i] = {"file": p, "error": str(e)}
-    dev = torch.device(device)
+    for (sr, _), clips in native.items():
+        clips.sort(key=lambda it: it[1].size(1))
+        for k in range(0, len(clips), max(1, batch_size)):
+            chunk = clips[k:k + max(1, batch_size)]
+            try:
+                for (i, _), a in zip(chunk, _resample_group([w for _, w in chunk], sr, dev)):
+                    items.append((i, a))
+            except Exception as e:
+                for i, _ in chunk:
+                    results[i] = {"file": paths[i], "error": str(e)}
     items.sort(key=lambda it: it[1].numel())  # neighbours of similar length: little padding
     for chunk in _batches(items, max(1, batch_size), ragged_supported(model.config.mel_bins)):
         try:
             ns = [a.numel() for _, a in chunk]
             S = max(ns)
-            audio = torch.zeros((len(chunk), S), dtype=torch.float32)
+            # clips resampled on the device stay there: the batch is then assembled on it
+            where = dev if any(a.device.type == "cuda" for _, a in chunk) else None
+            audio = torch.zeros((len(chunk), S), dtype=torch.float32, device=where)
             for j, (_, a) in enumerate(chunk):
                 audio[j, :ns[j]] = a.to(torch.float32)
             decoded = _decode_batch(model, audio.to(dev), decoder, timestamps, beam_width,
