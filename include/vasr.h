@@ -447,6 +447,40 @@ int vasr_resample_mix_f32(const float* x, int64_t ld_clip, int64_t ld_chan, int 
                           float* y, int64_t ld_y, int S_out, void* stream);
 int vasr_resample_tile_outputs(int orig, int nw);
 
+/* ------------------------------------------------------------------ long-form segmentation (device)
+ * A recording longer than the model accepts is cut at its quietest points.  A block is 320 samples
+ * (vasr_segment_block(): one token row, two mel hops); recording b is x[b*ld_x + i], i < samples[b]
+ * (device, optional; all S when NULL; values are clamped to [0, S]).
+ * vasr_block_energy_f64: E[b][k] = sum_{i ascending} (double)x[320k+i]^2 for the full blocks
+ *   k < samples[b] / 320, one float64 chain from 0 per block (a float32 product is exact in float64, so
+ *   the chain is the only rounding); 0 for the other k < S / 320.  Nothing at or past samples[b] is
+ *   read.  A workgroup owns vasr_segment_tile_blocks() consecutive blocks of one recording.
+ * vasr_segment_plan: the greedy rule on E, one workgroup per recording.  mB = ceil(min_samples / 320),
+ *   MB = max_samples / 320, nB = samples[b] / 320; p = 0; while samples[b] - 320 p > max_samples: among
+ *   the candidates c in [p + mB, min(p + MB, nB - mB)] take the smallest (score, c), score(c) =
+ *   E[c - W/2] + ... + E[c + W/2 - 1] summed ascending into one float64 from 0 (NaN counts as +inf);
+ *   cuts[b][n_cuts[b]++] = 320 c; p = c.  W = window_blocks is even and >= 2, mB >= W/2, MB >= 2 mB.
+ *   cuts is (B, max_cuts) int64 with row stride ld_cuts; max_cuts >= max(1, vasr_segment_max_cuts(S,
+ *   min_samples)) or the call is refused, and the kernel's loop stops at max_cuts.
+ * vasr_segment_max_cuts: the most cuts the rule can make in n samples, (n / 320) / mB; -1 for bad
+ *   arguments.
+ * vasr_segment_gather_f32: table (device) is (n_seg, 3) int64 rows (recording, start, length);
+ *   y[g][o] = x[recording][start + o] for o < length, 0 for length <= o < S_seg: the zero-padded batch
+ *   the front end reads, in one launch.  A row that does not lie inside its recording or has
+ *   length > S_seg is written as zeros.
+ * All sample offsets are 64-bit.  No allocation, no synchronisation, no host read; everything is
+ * enqueued on `stream`.  Argument errors return VASR_EINVAL before any device call. */
+int vasr_segment_block(void);
+int vasr_segment_tile_blocks(void);
+int64_t vasr_segment_max_cuts(int64_t n, int64_t min_samples);
+int vasr_block_energy_f64(const float* x, int64_t ld_x, int B, int S, const int32_t* samples, double* E,
+                          int64_t ld_e, void* stream);
+int vasr_segment_plan(const double* E, int64_t ld_e, int B, int S, const int32_t* samples, int64_t max_samples,
+                      int64_t min_samples, int window_blocks, int64_t* cuts, int64_t ld_cuts, int max_cuts,
+                      int32_t* n_cuts, void* stream);
+int vasr_segment_gather_f32(const float* x, int64_t ld_x, int B, int S, const int64_t* table, int n_seg,
+                            float* y, int64_t ld_y, int S_seg, void* stream);
+
 /* ------------------------------------------------------------------ mel front end
  * compute_mel_spectrogram (audio.py:65-143) is three launches:
  *  1. vasr_reflect_pad_f32: xp[b][0:S+2*pad] = reflect-padded audio (audio.py:100-101),

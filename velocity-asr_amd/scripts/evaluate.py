@@ -41,6 +41,10 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=16, help="Max equal-length files per device batch")
     p.add_argument("--lm", default=None, help="Bigram language model for beam search (.npz of BigramLM.save)")
     p.add_argument("--lm-weight", type=float, default=0.0, help="Weight of the language model score (0 = off)")
+    p.add_argument("--segment-seconds", type=float, default=None,
+                   help="Cut files longer than this at their quietest points and stitch the results (off by default)")
+    p.add_argument("--min-segment-seconds", type=float, default=None,
+                   help="Shortest segment of a cut file (a third of --segment-seconds by default)")
     args = p.parse_args(argv)
     if args.test_set is None and args.audio_dir is None:
         p.error("Either --test-set or --audio-dir must be specified")
@@ -68,7 +72,8 @@ def main(argv=None) -> int:
         rows = []
         for path, r in zip(files, transcribe_files(model, files, decoder, args.device, False,
                                                     args.batch_size, args.beam_width, lm=lm,
-                                                    lm_weight=args.lm_weight)):
+                                                    lm_weight=args.lm_weight, segment_seconds=args.segment_seconds,
+                                                    min_segment_seconds=args.min_segment_seconds)):
             if "error" in r:
                 logger.error(f"Error processing {path}: {r['error']}")
                 rows.append((path.name, f"[ERROR: {r['error']}]"))
@@ -93,7 +98,8 @@ def main(argv=None) -> int:
         return 0
     preds, refs = [], []
     results = transcribe_files(model, [a for a, _ in data], decoder, args.device, False,
-                               args.batch_size, args.beam_width, lm=lm, lm_weight=args.lm_weight)
+                               args.batch_size, args.beam_width, lm=lm, lm_weight=args.lm_weight,
+                               segment_seconds=args.segment_seconds, min_segment_seconds=args.min_segment_seconds)
     for (audio, ref), r in zip(data, results):
         if "error" in r:
             logger.error(f"Error processing {audio}: {r['error']}")

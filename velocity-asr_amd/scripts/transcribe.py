@@ -37,6 +37,10 @@ def parse_args(argv=None):
     p.add_argument("--timestamps", action="store_true", help="Include word-level timestamps")
     p.add_argument("--confidence", action="store_true",
                    help="Include a confidence per word and the greedy path's log-probability (implies --timestamps)")
+    p.add_argument("--segment-seconds", type=float, default=None,
+                   help="Cut files longer than this at their quietest points and stitch the results (off by default)")
+    p.add_argument("--min-segment-seconds", type=float, default=None,
+                   help="Shortest segment of a cut file (a third of --segment-seconds by default)")
     p.add_argument("--device", default="cuda", help="HIP device to run inference on")
     p.add_argument("--quiet", "-q", action="store_true", help="Suppress logging output")
     p.add_argument("--batch-size", type=int, default=16, help="Max equal-length files per device batch")
@@ -67,7 +71,9 @@ def main(argv=None) -> int:
             os.makedirs(args.output_dir, exist_ok=True)
         results = []
         for path, r in zip(files, transcribe_files(model, files, decoder, args.device, args.timestamps,
-                                                    args.batch_size, confidence=args.confidence)):
+                                                    args.batch_size, confidence=args.confidence,
+                                                    segment_seconds=args.segment_seconds,
+                                                    min_segment_seconds=args.min_segment_seconds)):
             if "error" in r:
                 logger.error(f"Error processing {path}: {r['error']}")
                 continue
@@ -92,7 +98,8 @@ def main(argv=None) -> int:
         logger.info(f"Processed {len(results)} files")
         return 0
 
-    r = transcribe_files(model, [args.audio], decoder, args.device, args.timestamps, 1, confidence=args.confidence)[0]
+    r = transcribe_files(model, [args.audio], decoder, args.device, args.timestamps, 1, confidence=args.confidence,
+                         segment_seconds=args.segment_seconds, min_segment_seconds=args.min_segment_seconds)[0]
     if "error" in r:
         logger.error(f"Error processing {args.audio}: {r['error']}")
         return 1

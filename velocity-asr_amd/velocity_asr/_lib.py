@@ -105,6 +105,14 @@ _SIGNATURES = {
     "vasr_resample_mix_f32": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 3 + [c_p, c_p] + [ctypes.c_int] * 3
                               + [c_p, c_i64, ctypes.c_int, c_p], ctypes.c_int),
     "vasr_resample_tile_outputs": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "vasr_segment_block": ([], ctypes.c_int),
+    "vasr_segment_tile_blocks": ([], ctypes.c_int),
+    "vasr_segment_max_cuts": ([c_i64, c_i64], c_i64),
+    "vasr_block_energy_f64": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_p, c_i64, c_p], ctypes.c_int),
+    "vasr_segment_plan": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, c_i64, c_i64, ctypes.c_int, c_p, c_i64,
+                           ctypes.c_int, c_p, c_p], ctypes.c_int),
+    "vasr_segment_gather_f32": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, ctypes.c_int, c_p, c_i64, ctypes.c_int,
+                                 c_p], ctypes.c_int),
     "vasr_reflect_pad_f32": ([c_p, c_i64, c_p, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p], ctypes.c_int),
     "vasr_mel_log_norm_f32": ([c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p],
                               ctypes.c_int),

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -199,6 +199,157 @@ def resample_on_device(x: torch.Tensor, orig_freq: int, new_freq: int, lengths=N
     if min(lengths) < S:
         samples = torch.tensor(lengths, dtype=torch.int32).to(x.device)
     return ops.resample_mix(x, tb.taps, tb.orig, tb.nw, tb.width, samples=samples), out_lengths
+
+
+# ---------------------------------------------------------------- long-form segmentation (extension)
+# A recording longer than the model accepts is cut at its quietest points into segments of between
+# min_samples and max_samples samples.  The rule below is the specification; the HIP kernels
+# (csrc/segment.hip) follow the order of every sum in it, so both give the same cuts exactly.
+SEGMENT_BLOCK = ops.SEGMENT_BLOCK  # 320 samples: one token row (two mel hops), so cuts fall on frames and rows
+SEGMENT_SECONDS, MIN_SEGMENT_SECONDS, SEGMENT_WINDOW_BLOCKS = 30.0, 10.0, 10  # 0.2 s window
+
+
+def check_segment_params(max_samples: int, min_samples: int, window_blocks: int = SEGMENT_WINDOW_BLOCKS,
+                         max_rows: Optional[int] = None) -> Tuple[int, int, int]:
+    """Validate the segmentation parameters (ValueError with the reason) -> (MB, mB, W).
+    max_rows: the model's positional table length (pe_time.shape[0]) where a model is known."""
+    M, m, W = int(max_samples), int(min_samples), int(window_blocks)
+    if W < 2 or W % 2:
+        raise ValueError(f"segmentation: window_blocks must be even and at least 2, got {W}")
+    if m < 1 or M < 1:
+        raise ValueError(f"segmentation: min_samples and max_samples must be positive, got {m} and {M}")
+    MB, mB = M // SEGMENT_BLOCK, -(-m // SEGMENT_BLOCK)
+    if mB < W // 2:
+        raise ValueError(f"segmentation: min_samples {m} ({mB} blocks) is under half the window of {W} blocks")
+    if MB < 2 * mB:
+        raise ValueError(f"segmentation: max_samples {M} holds {MB} blocks of {SEGMENT_BLOCK}, fewer than twice the "
+                         f"{mB} of min_samples {m}")
+    if m <= N_FFT // 2:
+        raise ValueError(f"segmentation: min_samples {m} must exceed the front end's reflect padding of {N_FFT // 2}")
+    if max_rows is not None:
+        rows = (M // HOP_LENGTH + 2) // 2  # token rows of M samples: frames M // hop + 1, stride 2 rounded up
+        if rows > int(max_rows):
+            raise ValueError(f"segmentation: max_samples {M} gives {rows} token rows, over the model's positional "
+                             f"table of {int(max_rows)}")
+    return MB, mB, W
+
+
+def block_energy_host(x: np.ndarray) -> np.ndarray:
+    """E[k] of the full 320-sample blocks of a float32 signal: acc += float64(x) * float64(x) over the
+    block's samples in ascending order, one float64 accumulator per block (the loop over i is the
+    order; numpy only runs the blocks side by side).  The product of two float32 values is exact in
+    float64, so the chain is the only rounding."""
+    x = np.asarray(x, np.float32)
+    nB = x.shape[0] // SEGMENT_BLOCK
+    b = x[:nB * SEGMENT_BLOCK].astype(np.float64).reshape(nB, SEGMENT_BLOCK)
+    acc = np.zeros(nB, np.float64)
+    for i in range(SEGMENT_BLOCK):
+        acc = acc + b[:, i] * b[:, i]
+    return acc
+
+
+def plan_cuts_host(E: np.ndarray, n: int, max_samples: int, min_samples: int,
+                   window_blocks: int = SEGMENT_WINDOW_BLOCKS) -> List[int]:
+    """The greedy plan on block energies E of a recording of n samples -> cut positions in samples.
+    score(c) = E[c - W/2] + ... + E[c + W/2 - 1] summed ascending into one float64 from 0 (NaN counts
+    as +inf); each cut is the candidate of [p + mB, min(p + MB, nB - mB)] with the smallest score,
+    ties to the lowest c."""
+    MB, mB, W = check_segment_params(max_samples, min_samples, window_blocks)
+    M, n = int(max_samples), int(n)
+    nB = n // SEGMENT_BLOCK
+    E = np.asarray(E, np.float64)
+    cuts: List[int] = []
+    p = 0
+    while n - p * SEGMENT_BLOCK > M:
+        c = np.arange(p + mB, min(p + MB, nB - mB) + 1)
+        s = np.zeros(c.shape[0], np.float64)
+        for k in range(-(W // 2), W // 2):
+            s = s + E[c + k]
+        s[np.isnan(s)] = np.inf
+        p = int(c[int(np.argmin(s))])  # argmin: the first of equal minima, the lowest c
+        cuts.append(p * SEGMENT_BLOCK)
+    return cuts
+
+
+def plan_segments_host(x: np.ndarray, max_samples: int, min_samples: int,
+                       window_blocks: int = SEGMENT_WINDOW_BLOCKS) -> List[int]:
+    """Cut positions of one float32 recording by the rule (numpy; the specification)."""
+    check_segment_params(max_samples, min_samples, window_blocks)
+    x = np.asarray(x, np.float32).reshape(-1)
+    return plan_cuts_host(block_energy_host(x), x.shape[0], max_samples, min_samples, window_blocks)
+
+
+def _segment_lengths(audio: torch.Tensor, lengths) -> List[int]:
+    if audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"segmentation: expected (B, S) audio with B, S >= 1, got {tuple(audio.shape)}")
+    B, S = audio.shape
+    lengths = [S] * B if lengths is None else [int(v) for v in lengths]
+    if len(lengths) != B or not all(0 <= v <= S for v in lengths):
+        raise ValueError(f"segmentation: lengths must be {B} sample counts in [0, {S}], got {lengths}")
+    return lengths
+
+
+def plan_segments(audio: torch.Tensor, lengths=None, *, max_samples: int = int(SEGMENT_SECONDS * SAMPLE_RATE),
+                  min_samples: int = int(MIN_SEGMENT_SECONDS * SAMPLE_RATE),
+                  window_blocks: int = SEGMENT_WINDOW_BLOCKS) -> List[List[int]]:
+    """Where to cut long recordings (extension): audio (B, S) or (S,) float32, zero-padded to S, with
+    lengths[b] samples each (all S when None) -> per recording the ascending list of cut positions in
+    samples (empty when it has at most max_samples).  Segments partition the recording, every cut is
+    a multiple of 320 and every segment has between min_samples and max_samples samples.
+
+    A host tensor runs the numpy rule (plan_segments_host); a HIP tensor runs the kernels
+    (ops.block_energy, ops.segment_plan), whose cuts are the same exactly.  The device path copies the
+    small cut table to the host, its only synchronisation; the audio stays on the device."""
+    if audio.dim() == 1:
+        audio = audio.unsqueeze(0)
+    lengths = _segment_lengths(audio, lengths)
+    check_segment_params(max_samples, min_samples, window_blocks)
+    B, S = audio.shape
+    if audio.device.type != "cuda":
+        x = audio.detach().to(torch.float32).numpy()
+        return [plan_segments_host(x[b, :lengths[b]], max_samples, min_samples, window_blocks) for b in range(B)]
+    x = audio.detach().to(torch.float32)
+    if S < SEGMENT_BLOCK or max(lengths) <= int(max_samples):
+        return [[] for _ in range(B)]  # nothing to cut: no launch
+    samples = None
+    if min(lengths) < S:
+        samples = torch.tensor(lengths, dtype=torch.int32).to(x.device)
+    E = ops.block_energy(x, samples)
+    cuts, n_cuts = ops.segment_plan(E, S, max_samples, min_samples, window_blocks, samples=samples)
+    # one copy: the counts ride in a last column of the table
+    host = torch.cat([cuts, n_cuts.to(torch.int64).unsqueeze(1)], dim=1).cpu().numpy()
+    return [host[b, :int(host[b, -1])].tolist() for b in range(B)]
+
+
+def segment_table(lengths, cuts) -> List[Tuple[int, int, int]]:
+    """(recording, start, length) of every segment, recordings in order, from per-recording cuts."""
+    rows = []
+    for b, (n, cs) in enumerate(zip(lengths, cuts)):
+        edges = [0] + [int(c) for c in cs] + [int(n)]
+        if any(e1 <= e0 for e0, e1 in zip(edges, edges[1:])):
+            raise ValueError(f"segmentation: cuts {list(cs)} do not partition a recording of {n} samples")
+        rows += [(b, e0, e1 - e0) for e0, e1 in zip(edges, edges[1:])]
+    return rows
+
+
+def segment_on_device(audio: torch.Tensor, lengths, cuts):
+    """Gather the planned segments of HIP recordings (B, S) into the zero-padded batch the front end
+    reads (extension): -> (batch (n_seg, S_seg) float32, seg_lengths, table).  table: the host list
+    of (recording, start, length) rows in recording order; row g of batch holds that slice, bit
+    for bit, followed by exact zeros up to S_seg, the longest segment.  One launch
+    (ops.segment_gather); nothing returns to the host."""
+    if audio.device.type != "cuda":
+        raise RuntimeError(f"segment_on_device: tensor is on {audio.device}; pass a HIP tensor")
+    if audio.dim() == 1:
+        audio = audio.unsqueeze(0)
+    lengths = _segment_lengths(audio, lengths)
+    if len(cuts) != len(lengths):
+        raise ValueError(f"segment_on_device: {len(cuts)} cut lists for {len(lengths)} recordings")
+    table = segment_table(lengths, cuts)
+    seg_lengths = [r[2] for r in table]
+    dev_table = torch.tensor(table, dtype=torch.int64).to(audio.device)
+    batch = ops.segment_gather(audio.to(torch.float32), dev_table, max(seg_lengths))
+    return batch, seg_lengths, table
 
 
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:

@@ -866,6 +866,98 @@ def resample_mix(x: torch.Tensor, taps: Optional[torch.Tensor], orig: int, nw: i
     return y
 
 
+SEGMENT_BLOCK = 320  # samples per block of the segmenter: one token row, two mel hops (vasr_segment_block)
+
+
+def _recordings(name: str, audio: torch.Tensor) -> torch.Tensor:
+    """(B, S) float32 HIP recordings with unit stride along samples; the row stride is passed on."""
+    if not isinstance(audio, torch.Tensor):
+        raise ValueError(f"{name}: expected a tensor")
+    if audio.device.type != "cuda":
+        raise RuntimeError(f"{name}: tensor is on {audio.device}; velocity_asr (MI355X build) runs on HIP devices only")
+    if audio.dtype != torch.float32:
+        raise ValueError(f"{name}: expected float32, got {audio.dtype}")
+    if audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"{name}: expected (B, S) with B, S >= 1, got {tuple(audio.shape)}")
+    if audio.shape[0] > 65535:
+        raise ValueError(f"{name}: at most 65535 recordings per launch, got {audio.shape[0]}")
+    if audio.shape[1] >= 2 ** 31:
+        raise ValueError(f"{name}: at most 2^31 - 1 samples per recording, got {audio.shape[1]}")
+    if (audio.shape[1] > 1 and audio.stride(1) != 1) or (audio.shape[0] > 1 and audio.stride(0) < audio.shape[1]):
+        audio = audio.contiguous()
+    return audio
+
+
+def block_energy(audio: torch.Tensor, samples: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, S) float32 recordings -> E (B, S // 320) float64 (vasr_block_energy_f64): per block of 320
+    samples the ascending float64 chain of its squared samples, 0 for blocks that are not wholly
+    inside samples[b] (int32 (B,), all S when None).  Nothing at or past samples[b] is read."""
+    audio = _recordings("block_energy.audio", audio)
+    B, S = audio.shape
+    samples = _lens("block_energy.samples", samples, B, audio.device)
+    nb = S // SEGMENT_BLOCK
+    E = torch.empty((B, nb), device=audio.device, dtype=torch.float64)
+    if nb == 0:  # no full block
+        return E
+    check(L.lib().vasr_block_energy_f64(audio.data_ptr(), audio.stride(0) if B > 1 else S, B, S, ptr(samples),
+                                        E.data_ptr(), nb, stream_of(audio)), "vasr_block_energy_f64")
+    return E
+
+
+def segment_plan(energy: torch.Tensor, S: int, max_samples: int, min_samples: int, window_blocks: int = 10,
+                 samples: Optional[torch.Tensor] = None, max_cuts: Optional[int] = None):
+    """The greedy cut plan on block energies (vasr_segment_plan): energy (B, S // 320) float64 from
+    block_energy of (B, S) recordings -> (cuts (B, max_cuts) int64 in samples, n_cuts (B,) int32);
+    only the first n_cuts[b] entries of a row are written.  max_cuts: columns of the table, by
+    default what vasr_segment_max_cuts gives for S (a narrower table is refused)."""
+    if not isinstance(energy, torch.Tensor) or energy.device.type != "cuda":
+        raise RuntimeError("segment_plan.energy: expected a HIP tensor")
+    if energy.dtype != torch.float64:
+        raise ValueError(f"segment_plan.energy: expected float64, got {energy.dtype}")
+    S, max_samples, min_samples, window_blocks = int(S), int(max_samples), int(min_samples), int(window_blocks)
+    if energy.dim() != 2 or energy.shape[0] < 1 or S < 1 or S >= 2 ** 31 or energy.shape[1] != S // SEGMENT_BLOCK:
+        raise ValueError(f"segment_plan: energy must be (B, {S // SEGMENT_BLOCK}) for {S} samples, got "
+                         f"{tuple(energy.shape)}")
+    if min_samples < 1 or max_samples < 1:
+        raise ValueError(f"segment_plan: bad segment bounds ({min_samples}, {max_samples})")
+    energy = energy.contiguous()
+    B = energy.shape[0]
+    samples = _lens("segment_plan.samples", samples, B, energy.device)
+    if max_cuts is None:
+        max_cuts = max(1, int(L.lib().vasr_segment_max_cuts(S, min_samples)))
+    max_cuts = int(max_cuts)
+    if max_cuts < 1:
+        raise ValueError(f"segment_plan: max_cuts must be at least 1, got {max_cuts}")
+    cuts = torch.zeros((B, max_cuts), device=energy.device, dtype=torch.int64)
+    n_cuts = torch.zeros((B,), device=energy.device, dtype=torch.int32)
+    rc = L.lib().vasr_segment_plan(energy.data_ptr(), energy.shape[1], B, S, ptr(samples), max_samples, min_samples,
+                                   window_blocks, cuts.data_ptr(), max_cuts, max_cuts, n_cuts.data_ptr(),
+                                   stream_of(energy))
+    if rc == -1:  # a parameter or table-width error, stated by the library
+        raise ValueError(L.lib().vasr_last_error().decode(errors="replace"))
+    check(rc, "vasr_segment_plan")
+    return cuts, n_cuts
+
+
+def segment_gather(audio: torch.Tensor, table: torch.Tensor, S_seg: int) -> torch.Tensor:
+    """(B, S) recordings and a device table (n_seg, 3) int64 of (recording, start, length) rows ->
+    the (n_seg, S_seg) zero-padded batch of the segments in one launch (vasr_segment_gather_f32)."""
+    audio = _recordings("segment_gather.audio", audio)
+    if not isinstance(table, torch.Tensor) or table.device != audio.device or table.dtype != torch.int64 \
+            or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or not table.is_contiguous():
+        raise ValueError(f"segment_gather.table: expected a contiguous int64 (n_seg, 3) tensor on {audio.device}")
+    S_seg = int(S_seg)
+    if S_seg < 1 or table.shape[0] > 65535:
+        raise ValueError(f"segment_gather: {table.shape[0]} segments of up to {S_seg} samples; 1 to 65535 segments of "
+                         "at least one sample")
+    B, S = audio.shape
+    y = torch.empty((table.shape[0], S_seg), device=audio.device, dtype=torch.float32)
+    check(L.lib().vasr_segment_gather_f32(audio.data_ptr(), audio.stride(0) if B > 1 else S, B, S, table.data_ptr(),
+                                          table.shape[0], y.data_ptr(), S_seg, S_seg, stream_of(audio)),
+          "vasr_segment_gather_f32")
+    return y
+
+
 def mel_log_norm(power: torch.Tensor, ld_power: int, stride_power: int, fb_csr, B: int, F: int, n_mels: int,
                  normalize: bool, frames: Optional[torch.Tensor] = None, frame_pad: int = 0) -> torch.Tensor:
     """frames: per-utterance frame counts (int32 (B,), each <= F); frames past them are 0.

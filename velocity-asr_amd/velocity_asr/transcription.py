@@ -12,6 +12,9 @@ has no per-length kernels (VASR_STFT=gemm, n_mels > 85) batches hold clips of on
 Files that are not at 16 kHz are downmixed and resampled on the device as well (grouped by rate
 and channel count, audio.resample_on_device: the host resampler's values bit for bit) and their
 16 kHz samples stay there; VASR_DEVICE_RESAMPLE=0 or an installed torchaudio keeps the host path.
+With segment_seconds a recording longer than that is cut on the device at its quietest points
+(audio.plan_segments), its segments join the batches as clips of their own and their tokens, spans
+and log-probabilities are stitched back into one result (stitch_segments).
 """
 
 from __future__ import annotations
@@ -24,9 +27,10 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
-from .audio import (HOP_LENGTH, N_FFT, SAMPLE_RATE, _FUSED_DOWNMIX_CHANNELS, _to_host_rate, device_resample_supported,
-                    load_audio, mel_on_device, ragged_supported, read_audio, resample_on_device)
-from .decode import CTCDecoder, _scored_from_device
+from .audio import (HOP_LENGTH, N_FFT, SAMPLE_RATE, SEGMENT_BLOCK, SEGMENT_WINDOW_BLOCKS, _FUSED_DOWNMIX_CHANNELS,
+                    _to_host_rate, check_segment_params, device_resample_supported, load_audio, mel_on_device,
+                    plan_segments, ragged_supported, read_audio, resample_on_device, segment_on_device)
+from .decode import CTCDecoder, _scored_from_device, token_confidences
 
 logger = logging.getLogger(__name__)
 
@@ -87,11 +91,13 @@ def group_words(tokens: Sequence[int], spans: Sequence[Tuple[int, int]], vocabul
 
 def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: bool,
                   beam_width: int = 1, lengths: Optional[List[int]] = None, lm=None,
-                  lm_weight: float = 0.0, confidence: bool = False) -> List[Tuple]:
+                  lm_weight: float = 0.0, confidence: bool = False, raw: bool = False) -> List:
     """(b, S) device audio -> [(text, words or None)] through the device pipeline.  lengths:
     per-clip sample counts when the clips were zero-padded to S.  lm / lm_weight: language model
     for the beam search (decode.BigramLM runs on the device).  confidence (greedy only):
-    [(text, words with "confidence", path log-probability)] from model.greedy_scored."""
+    [(text, words with "confidence", path log-probability)] from model.greedy_scored.
+    raw: per clip the integer arrays instead of text (a dict as stitch_segments takes and _render
+    turns into the tuple above): what the segments of a long recording are stitched from."""
     with torch.no_grad():
         mel = mel_on_device(audio, n_mels=model.config.mel_bins, lengths=lengths,
                             frame_pad=model.temporal_binding.conv_padding())
@@ -100,10 +106,21 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
             logits = model(mel, frames=frames)
             # one search launch for the batch: each clip's workgroup stops at its own row count
             rows = None if frames is None else [model.get_output_length(f) for f in frames]
+            if raw:  # each clip's best hypothesis
+                beams = decoder.decode_beam_search(logits, beam_width=beam_width, return_all_beams=True,
+                                                   input_lengths=rows, lm_scorer=lm, lm_weight=lm_weight)
+                return [{"tokens": list(r[0].tokens) if r else []} for r in beams]
             return [(t, None) for t in decoder.decode_beam_search(logits, beam_width=beam_width, input_lengths=rows,
                                                                   lm_scorer=lm, lm_weight=lm_weight)]
         if confidence:
             # the head's GEMM leaves each frame's argmax and log-sum-exp (no logits in HBM either)
+            if raw:
+                res = model.greedy_scored(mel, frames=frames, blank=decoder.blank_token)
+                toks, lens, st, en, lsum, lmin, path = (t.cpu().numpy() for t in res)
+                return [{"tokens": toks[b, :n].tolist(), "start": st[b, :n].tolist(), "end": en[b, :n].tolist(),
+                         "logp_sum": lsum[b, :n].tolist(), "logp_min": lmin[b, :n].tolist(),
+                         "run_lengths": (en[b, :n] - st[b, :n]).tolist(), "path_logp": float(path[b])}
+                        for b, n in enumerate(int(v) for v in lens)]
             scored = _scored_from_device(model.greedy_scored(mel, frames=frames, blank=decoder.blank_token), "mean")
             out = []
             for r in scored:
@@ -119,6 +136,14 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
     toks, lens = toks.cpu().numpy(), lens.cpu().numpy()
     if timestamps:
         st, en = st.cpu().numpy(), en.cpu().numpy()
+    if raw:
+        out = []
+        for b, n in enumerate(int(v) for v in lens):
+            r = {"tokens": toks[b, :n].tolist()}
+            if timestamps:
+                r["start"], r["end"] = st[b, :n].tolist(), en[b, :n].tolist()
+            out.append(r)
+        return out
     out = []
     for b in range(toks.shape[0]):
         n = int(lens[b])
@@ -128,6 +153,59 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
             out.append((" ".join(w["word"] for w in words), words))
         else:
             out.append((decoder._tokens_to_text(ids), None))
+    return out
+
+
+def _render(r: Dict, decoder: CTCDecoder, timestamps: bool, confidence: bool) -> Tuple:
+    """A raw decoding (_decode_batch(raw=True), or stitch_segments of several) -> the tuple
+    _decode_batch returns for a clip: (text, words or None[, path log-probability])."""
+    if "start" not in r or not timestamps:  # beam search, or greedy without time spans
+        return (decoder._tokens_to_text(r["tokens"]), None)
+    spans = [(int(s), int(e)) for s, e in zip(r["start"], r["end"])]
+    if confidence:
+        conf = token_confidences(r["logp_sum"], r["logp_min"], [e - s for s, e in spans], "mean")
+        words = group_words(r["tokens"], spans, decoder.vocabulary, conf)
+        return (" ".join(w["word"] for w in words), words, float(r["path_logp"]))
+    words = group_words(r["tokens"], spans, decoder.vocabulary)
+    return (" ".join(w["word"] for w in words), words)
+
+
+_STITCH_LISTS = ("tokens", "start", "end", "logp_sum", "logp_min", "run_lengths")
+
+
+def stitch_segments(segments: Sequence[Dict], starts: Sequence[int]) -> Dict:
+    """Join the decodings of a recording's consecutive segments into one (pure host arithmetic).
+
+    segments: one dict per segment, in order, with "tokens" and, where the decode produced them,
+    "start" / "end" (token-row spans within the segment, as csrc/decode.hip writes them and
+    group_words reads them: row t covers samples from 320 t), "logp_sum", "logp_min", "run_lengths"
+    (one value per token) and "path_logp".  starts: each segment's first sample in the recording, a
+    multiple of 320 (cuts are).  Returns one dict with the same keys: the lists concatenated in
+    segment order, the spans shifted by start // 320 as integers (seconds are formed once, later,
+    from the shifted rows) and path_logp the float64 sum of the segments' values in segment order.
+    A segment without tokens contributes nothing but its path_logp.  Words are not formed here:
+    group_words runs once over the joined stream, so a segment that begins inside a word continues
+    it (word boundaries come from the separator tokens, not from the cuts)."""
+    if len(segments) != len(starts) or not segments:
+        raise ValueError(f"stitch_segments: {len(segments)} segments with {len(starts)} start samples")
+    keys = [k for k in _STITCH_LISTS if k in segments[0]]
+    out: Dict = {k: [] for k in keys}
+    score = 0.0  # a Python float is a float64
+    for seg, start in zip(segments, starts):
+        start = int(start)
+        if start < 0 or start % SEGMENT_BLOCK:
+            raise ValueError(f"stitch_segments: segment start {start} is not a non-negative multiple of {SEGMENT_BLOCK}")
+        n = len(seg["tokens"])
+        shift = start // SEGMENT_BLOCK
+        for k in keys:
+            v = list(seg[k])
+            if len(v) != n:
+                raise ValueError(f"stitch_segments: {len(v)} values of {k!r} for {n} tokens")
+            out[k] += [int(t) + shift for t in v] if k in ("start", "end") else v
+        if "path_logp" in segments[0]:
+            score = score + float(seg["path_logp"])
+    if "path_logp" in segments[0]:
+        out["path_logp"] = score
     return out
 
 
@@ -176,7 +254,8 @@ def _resample_group(clips: List[torch.Tensor], sr: int, dev: torch.device) -> Li
 
 def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timestamps: bool = False,
                      batch_size: int = 16, beam_width: int = 1, lm=None, lm_weight: float = 0.0,
-                     confidence: bool = False) -> List[Dict]:
+                     confidence: bool = False, segment_seconds: Optional[float] = None,
+                     min_segment_seconds: Optional[float] = None) -> List[Dict]:
     """Transcribe audio files; returns one result dict per file in input order.  lm / lm_weight:
     language model for beam_width > 1 (a decode.BigramLM is fused on the device).
     confidence (extension, greedy only; implies timestamps): each word also carries
@@ -186,10 +265,27 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
     A result is {"file", "duration", "transcription"} (+ "words" with timestamps), as the
     reference's transcribe_file returns; a file that fails gets {"file", "error"} instead,
     so callers can log it the way the reference's per-file try/except does.
+
+    segment_seconds / min_segment_seconds (extension): None keeps a recording whole, and one over
+    the model's positional table (about 100 s) fails.  With a value, every file longer than
+    segment_seconds is cut on the device at its quietest points into segments of between
+    min_segment_seconds (a third of segment_seconds when None) and segment_seconds
+    (audio.plan_segments); the segments share the batches with the other files, each is decoded as
+    a clip of its own (beam search: each alone, best hypotheses joined) and stitch_segments joins
+    them, so "duration" is the recording's and words run across the cuts.  A file with a segment
+    that fails gets {"file", "error"}.
     """
     if confidence and beam_width > 1:
         raise ValueError("transcribe_files: confidence is reported for greedy decoding (beam_width = 1)")
     timestamps = timestamps or confidence
+    seg_max = seg_min = None
+    if segment_seconds is not None:
+        seg_max = int(round(float(segment_seconds) * SAMPLE_RATE))
+        seg_min = seg_max // 3 if min_segment_seconds is None else int(round(float(min_segment_seconds) * SAMPLE_RATE))
+        pe = getattr(getattr(getattr(model, "temporal_binding", None), "pos_encoding", None), "pe_time", None)
+        check_segment_params(seg_max, seg_min, SEGMENT_WINDOW_BLOCKS, max_rows=None if pe is None else pe.shape[0])
+    elif min_segment_seconds is not None:
+        raise ValueError("transcribe_files: min_segment_seconds needs segment_seconds")
     paths = [str(p) for p in paths]
     results: List[Optional[Dict]] = [None] * len(paths)
     items: List[Tuple[int, torch.Tensor]] = []
@@ -232,6 +328,25 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
             except Exception as e:
                 for i, _ in chunk:
                     results[i] = {"file": paths[i], "error": str(e)}
+    # long recordings: planned and gathered where the audio is (or goes), keyed (file, k) from here on
+    long_files: Dict[int, Tuple[int, List[int]]] = {}  # file -> (samples, start of each segment)
+    seg_raw: Dict[Tuple[int, int], Dict] = {}
+    seg_errors: Dict[int, str] = {}
+    if seg_max is not None:
+        whole, items = items, []
+        for i, a in whole:
+            n = a.numel()
+            if n <= seg_max:
+                items.append((i, a))
+                continue
+            try:
+                rec = a.to(device=dev, dtype=torch.float32).unsqueeze(0)
+                cuts = plan_segments(rec, [n], max_samples=seg_max, min_samples=seg_min)
+                batch, seg_lengths, table = segment_on_device(rec, [n], cuts)
+                long_files[i] = (n, [start for _, start, _ in table])
+                items += [((i, k), batch[k, :m]) for k, m in enumerate(seg_lengths)]
+            except Exception as e:
+                results[i] = {"file": paths[i], "error": str(e)}
     items.sort(key=lambda it: it[1].numel())  # neighbours of similar length: little padding
     for chunk in _batches(items, max(1, batch_size), ragged_supported(model.config.mel_bins)):
         try:
@@ -242,10 +357,16 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
             audio = torch.zeros((len(chunk), S), dtype=torch.float32, device=where)
             for j, (_, a) in enumerate(chunk):
                 audio[j, :ns[j]] = a.to(torch.float32)
+            segmented = any(isinstance(key, tuple) for key, _ in chunk)
             decoded = _decode_batch(model, audio.to(dev), decoder, timestamps, beam_width,
                                     lengths=None if min(ns) == S else ns, lm=lm, lm_weight=lm_weight,
-                                    confidence=confidence)
+                                    confidence=confidence, raw=segmented)
             for (i, _), n, dec in zip(chunk, ns, decoded):
+                if isinstance(i, tuple):  # a segment: kept raw until its file is whole
+                    seg_raw[i] = dec
+                    continue
+                if segmented:
+                    dec = _render(dec, decoder, timestamps, confidence)
                 r = {"file": paths[i], "duration": n / SAMPLE_RATE, "transcription": dec[0]}
                 if timestamps:
                     r["words"] = dec[1]
@@ -254,7 +375,22 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
                 results[i] = r
         except Exception as e:
             for i, _ in chunk:
-                results[i] = {"file": paths[i], "error": str(e)}
+                if isinstance(i, tuple):
+                    seg_errors.setdefault(i[0], str(e))
+                else:
+                    results[i] = {"file": paths[i], "error": str(e)}
+    for i, (n, starts) in long_files.items():
+        if i in seg_errors:
+            results[i] = {"file": paths[i], "error": seg_errors[i]}
+            continue
+        dec = _render(stitch_segments([seg_raw[(i, k)] for k in range(len(starts))], starts), decoder, timestamps,
+                      confidence)
+        r = {"file": paths[i], "duration": n / SAMPLE_RATE, "transcription": dec[0]}
+        if timestamps:
+            r["words"] = dec[1]
+        if confidence:
+            r["score"] = dec[2]
+        results[i] = r
     return results  # type: ignore[return-value]
 
 
