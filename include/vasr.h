@@ -481,6 +481,33 @@ int vasr_segment_plan(const double* E, int64_t ld_e, int B, int S, const int32_t
 int vasr_segment_gather_f32(const float* x, int64_t ld_x, int B, int S, const int64_t* table, int n_seg,
                             float* y, int64_t ld_y, int S_seg, void* stream);
 
+/* ------------------------------------------------------------------ WER / CER scoring (device)
+ * Substitution, deletion and insertion counts of P independent pairs of int32 id sequences, the rule
+ * velocity_asr.training.edit_counts_host states: c[0][0] = (0,0,0), c[i][0] = i insertions,
+ * c[0][j] = j deletions; for i, j >= 1, c[i][j] = c[i-1][j-1] when hyp[i-1] == ref[j-1], otherwise the
+ * candidate of the smallest S + D + I among substitution (c[i-1][j-1], S + 1), deletion (c[i][j-1],
+ * D + 1) and insertion (c[i-1][j], I + 1), ties to the first in that order.  The counts travel with
+ * the cost: no table, no backtrace.  Integer only, so the result equals the host rule bit for bit.
+ * vasr_edit_counts_i32: pair p is hyp[p*ld_hyp + i], i < min(hyp_len[p], max_hyp), against
+ *   ref[p*ld_ref + j], j < min(ref_len[p], max_ref) (negative lengths count as 0); nothing past a
+ *   pair's length reaches the result.  counts is (P, 3) int32: S, D, I.  1 <= P <= 65535 and
+ *   0 <= max_hyp, max_ref <= 65535, so every count fits 16 bits and a cell is one 64-bit word
+ *   (cost, S, D, I).  The reference lies on the columns.  A pair of at most vasr_edit_wave_cols()
+ *   reference items is swept by one wave (several pairs per workgroup, no barrier); a wider one by
+ *   one workgroup, in passes of vasr_edit_tile_cols() columns whose last column is kept in the
+ *   workspace between passes.  One call takes any mix of the two.
+ * vasr_edit_workspace_bytes: bytes vasr_edit_counts_i32 needs at `workspace` (0 when max_ref fits one
+ *   pass; workspace may then be NULL); -1 for arguments outside the limits above.  The workspace is
+ *   written before it is read.
+ * All arrays are on the device.  No allocation, no synchronisation, no host read; everything is
+ * enqueued on `stream`.  Argument errors return VASR_EINVAL before any device call. */
+int vasr_edit_counts_i32(const int32_t* hyp, int64_t ld_hyp, const int32_t* hyp_len, int max_hyp,
+                         const int32_t* ref, int64_t ld_ref, const int32_t* ref_len, int max_ref,
+                         int P, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t vasr_edit_workspace_bytes(int P, int max_hyp, int max_ref);
+int vasr_edit_wave_cols(void);
+int vasr_edit_tile_cols(void);
+
 /* ------------------------------------------------------------------ mel front end
  * compute_mel_spectrogram (audio.py:65-143) is three launches:
  *  1. vasr_reflect_pad_f32: xp[b][0:S+2*pad] = reflect-padded audio (audio.py:100-101),

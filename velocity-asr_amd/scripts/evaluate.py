@@ -9,6 +9,8 @@ Same command line and printed report as the reference's scripts/evaluate.py:
 --test-set takes a TSV manifest (`audio_path<TAB>reference text`); the reference's
 dataset loader is a stub that loads nothing. --beam-width > 1 selects prefix beam search, one
 launch per batch; --lm FILE.npz --lm-weight X fuses a bigram table (decode.BigramLM.save) into it.
+WER and CER are scored on --device (one batched edit-distance launch per unit); --error-breakdown adds the
+substitution / deletion / insertion totals to the report, --per-utterance FILE writes them per file.
 """
 
 import argparse
@@ -16,11 +18,13 @@ import logging
 import sys
 from pathlib import Path
 
+import torch
+
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from velocity_asr import VELOCITYASR, CTCDecoder, create_default_vocabulary  # noqa: E402
 from velocity_asr.decode import BigramLM  # noqa: E402
-from velocity_asr.training import compute_cer, compute_wer  # noqa: E402
+from velocity_asr.training import error_counts, error_rate  # noqa: E402
 from velocity_asr.transcription import find_audio_files, load_manifest, transcribe_files  # noqa: E402
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s | %(levelname)s | %(message)s",
@@ -45,6 +49,10 @@ def parse_args(argv=None):
                    help="Cut files longer than this at their quietest points and stitch the results (off by default)")
     p.add_argument("--min-segment-seconds", type=float, default=None,
                    help="Shortest segment of a cut file (a third of --segment-seconds by default)")
+    p.add_argument("--error-breakdown", action="store_true",
+                   help="With --test-set: append the word and character substitution/deletion/insertion totals")
+    p.add_argument("--per-utterance", default=None, metavar="FILE",
+                   help="With --test-set: write one TSV row per scored file (path, reference words, word S, D, I, WER)")
     args = p.parse_args(argv)
     if args.test_set is None and args.audio_dir is None:
         p.error("Either --test-set or --audio-dir must be specified")
@@ -96,7 +104,7 @@ def main(argv=None) -> int:
     if not data:
         logger.error("No test data loaded. Exiting.")
         return 0
-    preds, refs = [], []
+    preds, refs, paths = [], [], []
     results = transcribe_files(model, [a for a, _ in data], decoder, args.device, False,
                                args.batch_size, args.beam_width, lm=lm, lm_weight=args.lm_weight,
                                segment_seconds=args.segment_seconds, min_segment_seconds=args.min_segment_seconds)
@@ -106,9 +114,23 @@ def main(argv=None) -> int:
             continue
         preds.append(r["transcription"])
         refs.append(ref)
-    wer, cer = compute_wer(preds, refs), compute_cer(preds, refs)
+        paths.append(audio)
+    # scored on the device when it is a HIP device (the same integers as the host rule, divided once)
+    score_device = args.device if torch.device(args.device).type == "cuda" else None
+    words = error_counts(preds, refs, "word", score_device)
+    chars = error_counts(preds, refs, "char", score_device)
+    wer, cer = error_rate(words), error_rate(chars)
     report = [f"Test Set: {args.test_set}", f"Samples: {len(preds)}",
               f"WER: {wer * 100:.2f}%", f"CER: {cer * 100:.2f}%"]
+    if args.error_breakdown:
+        for name, cs in (("Word", words), ("Char", chars)):
+            report.append(f"{name} S/D/I/N: {sum(c.substitutions for c in cs)}/{sum(c.deletions for c in cs)}/"
+                          f"{sum(c.insertions for c in cs)}/{sum(c.ref_length for c in cs)}")
+    if args.per_utterance:
+        with open(args.per_utterance, "w", encoding="utf-8") as f:
+            for path, c in zip(paths, words):
+                f.write(f"{path}\t{c.ref_length}\t{c.substitutions}\t{c.deletions}\t{c.insertions}\t{c.rate:.6f}\n")
+        logger.info(f"Per-utterance counts saved to {args.per_utterance}")
     print("\n" + RULE)
     print("EVALUATION RESULTS")
     print(RULE)

@@ -113,6 +113,11 @@ _SIGNATURES = {
                            ctypes.c_int, c_p, c_p], ctypes.c_int),
     "vasr_segment_gather_f32": ([c_p, c_i64, ctypes.c_int, ctypes.c_int, c_p, ctypes.c_int, c_p, c_i64, ctypes.c_int,
                                  c_p], ctypes.c_int),
+    "vasr_edit_counts_i32": ([c_p, c_i64, c_p, ctypes.c_int, c_p, c_i64, c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, c_i64,
+                              c_p], ctypes.c_int),
+    "vasr_edit_workspace_bytes": ([ctypes.c_int] * 3, c_i64),
+    "vasr_edit_wave_cols": ([], ctypes.c_int),
+    "vasr_edit_tile_cols": ([], ctypes.c_int),
     "vasr_reflect_pad_f32": ([c_p, c_i64, c_p, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p], ctypes.c_int),
     "vasr_mel_log_norm_f32": ([c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p],
                               ctypes.c_int),

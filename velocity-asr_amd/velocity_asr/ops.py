@@ -958,6 +958,56 @@ def segment_gather(audio: torch.Tensor, table: torch.Tensor, S_seg: int) -> torc
     return y
 
 
+EDIT_MAX_ITEMS = 65535  # items per sequence and pairs per launch of vasr_edit_counts_i32
+
+
+def _id_rows(name: str, t: torch.Tensor):
+    """(P, L) int32 HIP id rows with unit stride along items -> (tensor with data, row stride, L).  A
+    width of 0 is legal (every sequence empty); the library still wants a pointer."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a tensor")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{name}: tensor is on {t.device}; velocity_asr (MI355X build) runs on HIP devices only")
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError(f"{name}: expected int32 (P, L) with P >= 1, got {t.dtype} {tuple(t.shape)}")
+    P, n = t.shape
+    if n > EDIT_MAX_ITEMS:
+        raise ValueError(f"{name}: at most {EDIT_MAX_ITEMS} items per sequence, got {n}")
+    if n == 0:
+        return torch.empty((P, 1), device=t.device, dtype=torch.int32), 1, 0
+    if (n > 1 and t.stride(1) != 1) or (P > 1 and t.stride(0) < n):
+        t = t.contiguous()
+    return t, (t.stride(0) if P > 1 else n), n
+
+
+def edit_counts(hyp: torch.Tensor, ref: torch.Tensor, hyp_lengths: torch.Tensor, ref_lengths: torch.Tensor) -> torch.Tensor:
+    """Substitution, deletion and insertion counts of P pairs (vasr_edit_counts_i32): hyp (P, Lh) and ref
+    (P, Lr) int32 ids, lengths int32 (P,) clamped to [0, L]; rows may be views into wider matrices.
+    -> (P, 3) int32 on the device, equal to training.edit_counts_host of each pair.  No synchronisation;
+    more than 65535 pairs go in several launches."""
+    hyp, ld_h, mh = _id_rows("edit_counts.hyp", hyp)
+    ref, ld_r, mr = _id_rows("edit_counts.ref", ref)
+    P = hyp.shape[0]
+    if ref.shape[0] != P or ref.device != hyp.device:
+        raise ValueError(f"edit_counts: hyp has {P} rows on {hyp.device}, ref {ref.shape[0]} on {ref.device}")
+    hyp_lengths = _lens("edit_counts.hyp_lengths", hyp_lengths, P, hyp.device)
+    ref_lengths = _lens("edit_counts.ref_lengths", ref_lengths, P, hyp.device)
+    if hyp_lengths is None or ref_lengths is None:
+        raise ValueError("edit_counts: hyp_lengths and ref_lengths are required")
+    counts = torch.empty((P, 3), device=hyp.device, dtype=torch.int32)
+    lib = L.lib()
+    for p0 in range(0, P, EDIT_MAX_ITEMS):
+        n = min(EDIT_MAX_ITEMS, P - p0)
+        need = int(lib.vasr_edit_workspace_bytes(n, mh, mr))
+        if need < 0:
+            raise ValueError(f"edit_counts: sizes ({n}, {mh}, {mr}) outside the kernel's limits")
+        ws = torch.empty((need // 8,), device=hyp.device, dtype=torch.int64) if need else None
+        check(lib.vasr_edit_counts_i32(hyp[p0:].data_ptr(), ld_h, hyp_lengths[p0:].data_ptr(), mh, ref[p0:].data_ptr(),
+                                       ld_r, ref_lengths[p0:].data_ptr(), mr, n, counts[p0:].data_ptr(), ptr(ws), need,
+                                       stream_of(hyp)), "vasr_edit_counts_i32")
+    return counts
+
+
 def mel_log_norm(power: torch.Tensor, ld_power: int, stride_power: int, fb_csr, B: int, F: int, n_mels: int,
                  normalize: bool, frames: Optional[torch.Tensor] = None, frame_pad: int = 0) -> torch.Tensor:
     """frames: per-utterance frame counts (int32 (B,), each <= F); frames past them are 0.

@@ -27,11 +27,17 @@ probabilities is not built: refused in train mode with dropout > 0).  The layers
 LayerNorm, conv and sigmoid, which torch.autograd differentiates as torch ops.  The rest of training (a
 whole-model forward_differentiable, backward passes of the fused GEMM, tail and LayerNorm kernels, bf16,
 schedulers, Trainer) stays outside this build's scope.
+
+The metrics: compute_wer / compute_cer are the reference's (a Python Levenshtein loop) unless given a HIP
+device, in which case error_counts scores all pairs in one launch of the batched edit-distance kernel
+(vasr_edit_counts_i32) and they return the same float.  edit_counts_host is that kernel's specification:
+substitution, deletion and insertion counts carried forward with the cost.
 """
 
 from __future__ import annotations
 
-from typing import List, Sequence
+from dataclasses import dataclass
+from typing import List, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -327,8 +333,11 @@ def _edit_distance(a: Sequence, b: Sequence) -> int:
     return prev[len(b)]
 
 
-def compute_wer(predictions: List[str], references: List[str]) -> float:
-    """Word error rate: total word edits / total reference words (0.0 if no words)."""
+def compute_wer(predictions: List[str], references: List[str], device=None) -> float:
+    """Word error rate: total word edits / total reference words (0.0 if no words).  device: a HIP
+    device scores the pairs with the edit-distance kernel (error_counts); the float is the same."""
+    if device is not None:
+        return error_rate(error_counts(predictions, references, "word", device))
     errors = words = 0
     for pred, ref in zip(predictions, references):
         ref_words = ref.lower().split()
@@ -337,11 +346,137 @@ def compute_wer(predictions: List[str], references: List[str]) -> float:
     return errors / words if words > 0 else 0.0
 
 
-def compute_cer(predictions: List[str], references: List[str]) -> float:
-    """Character error rate: total char edits / total reference chars (0.0 if none)."""
+def compute_cer(predictions: List[str], references: List[str], device=None) -> float:
+    """Character error rate: total char edits / total reference chars (0.0 if none).  device: as
+    compute_wer."""
+    if device is not None:
+        return error_rate(error_counts(predictions, references, "char", device))
     errors = chars = 0
     for pred, ref in zip(predictions, references):
         ref_chars = list(ref.lower())
         errors += _edit_distance(list(pred.lower()), ref_chars)
         chars += len(ref_chars)
     return errors / chars if chars > 0 else 0.0
+
+
+def edit_counts_host(hyp: Sequence, ref: Sequence) -> Tuple[int, int, int]:
+    """(substitutions, deletions, insertions) of hyp against ref: the specification the device kernel
+    (vasr_edit_counts_i32) reproduces exactly.  c[i][j] are the counts of hyp[:i] against ref[:j]:
+    c[i][0] is i insertions, c[0][j] j deletions; equal items copy c[i-1][j-1] unconditionally (as
+    _edit_distance does), otherwise the candidate of the smallest S + D + I wins, ties going to the
+    first of substitution (c[i-1][j-1]), deletion (c[i][j-1]: a reference item with no counterpart),
+    insertion (c[i-1][j]: a hypothesis item with no counterpart).  The counts travel with the cost:
+    one row of memory, no backtrace.  S + D + I == _edit_distance(hyp, ref)."""
+    n = len(ref)
+    prev = [(0, j, 0) for j in range(n + 1)]
+    for i in range(1, len(hyp) + 1):
+        cur = [(0, 0, i)] + [None] * n
+        hi = hyp[i - 1]
+        for j in range(1, n + 1):
+            if hi == ref[j - 1]:
+                cur[j] = prev[j - 1]
+                continue
+            s, d, ins = prev[j - 1]
+            best, cost = (s + 1, d, ins), s + d + ins
+            s2, d2, i2 = cur[j - 1]
+            if s2 + d2 + i2 < cost:
+                best, cost = (s2, d2 + 1, i2), s2 + d2 + i2
+            s3, d3, i3 = prev[j]
+            if s3 + d3 + i3 < cost:
+                best = (s3, d3, i3 + 1)
+            cur[j] = best
+        prev = cur
+    return prev[n]
+
+
+@dataclass
+class ErrorCounts:
+    """Edit counts of one hypothesis against its reference."""
+
+    substitutions: int
+    deletions: int
+    insertions: int
+    ref_length: int
+    hyp_length: int
+
+    @property
+    def hits(self) -> int:
+        return self.ref_length - self.substitutions - self.deletions
+
+    @property
+    def errors(self) -> int:
+        return self.substitutions + self.deletions + self.insertions
+
+    @property
+    def rate(self) -> float:
+        return self.errors / self.ref_length if self.ref_length > 0 else 0.0
+
+
+def error_rate(counts: List[ErrorCounts]) -> float:
+    """Corpus rate of per-pair counts: summed errors over summed reference items, divided once (the
+    float compute_wer / compute_cer return); 0.0 if the references are empty."""
+    errors = sum(c.errors for c in counts)
+    items = sum(c.ref_length for c in counts)
+    return errors / items if items > 0 else 0.0
+
+
+MAX_DEVICE_ITEMS = ops.EDIT_MAX_ITEMS  # a longer sequence is scored on the host
+# error_counts(device=...) keeps a batch of fewer DP cells than this on the host: below it the upload,
+# launch and download cost more than the Python loop (profiles/score.md).
+MIN_DEVICE_CELLS = 1000
+
+
+def _is_hip(device) -> bool:
+    return device is not None and torch.device(device).type == "cuda"
+
+
+def error_counts(predictions: List[str], references: List[str], unit: str = "word", device=None) -> List[ErrorCounts]:
+    """Per-pair substitution / deletion / insertion counts.  The text normalisation is compute_wer's
+    (unit "word": .lower().split()) or compute_cer's ("char": list(.lower())).  device None (or a
+    non-HIP device) runs edit_counts_host.  A HIP device interns the items as int32 ids (one dictionary
+    per call), uploads the padded id matrices and lengths once, runs vasr_edit_counts_i32 and downloads
+    the (P, 3) counts once; a pair with a side longer than 65535 items is scored on the host in the
+    same call, and so is a batch of fewer than MIN_DEVICE_CELLS cells."""
+    if unit not in ("word", "char"):
+        raise ValueError(f"error_counts: unit must be 'word' or 'char', got {unit!r}")
+    split = (lambda s: s.lower().split()) if unit == "word" else (lambda s: list(s.lower()))
+    pairs = [(split(p), split(r)) for p, r in zip(predictions, references)]
+    out: List[ErrorCounts] = [None] * len(pairs)  # type: ignore[list-item]
+    on_device = []
+    if _is_hip(device):
+        on_device = [k for k, (h, r) in enumerate(pairs) if len(h) <= MAX_DEVICE_ITEMS and len(r) <= MAX_DEVICE_ITEMS]
+        if sum(len(pairs[k][0]) * len(pairs[k][1]) for k in on_device) < MIN_DEVICE_CELLS:
+            on_device = []
+    if on_device:
+        import numpy as np
+        ids: dict = {}
+        P = len(on_device)
+        mh = max(1, max(len(pairs[k][0]) for k in on_device))
+        mr = max(1, max(len(pairs[k][1]) for k in on_device))
+        # one host buffer, one upload: [hyp ids | ref ids | hyp lengths | ref lengths] per pair
+        buf = np.zeros((P, mh + mr + 2), np.int32)
+        for row, k in zip(buf, on_device):
+            h, r = pairs[k]
+            row[:len(h)] = [ids.setdefault(x, len(ids)) for x in h]
+            row[mh:mh + len(r)] = [ids.setdefault(x, len(ids)) for x in r]
+            row[mh + mr], row[mh + mr + 1] = len(h), len(r)
+        dev = torch.from_numpy(buf).to(device)
+        got = ops.edit_counts(dev[:, :mh], dev[:, mh:mh + mr], dev[:, mh + mr].contiguous(),
+                              dev[:, mh + mr + 1].contiguous()).cpu().tolist()
+        for k, (s, d, i) in zip(on_device, got):
+            out[k] = ErrorCounts(s, d, i, len(pairs[k][1]), len(pairs[k][0]))
+    for k, (h, r) in enumerate(pairs):
+        if out[k] is None:
+            s, d, i = edit_counts_host(h, r)
+            out[k] = ErrorCounts(s, d, i, len(r), len(h))
+    return out
+
+
+def token_error_counts(hyp_tokens: torch.Tensor, hyp_lengths: torch.Tensor, ref_tokens: torch.Tensor,
+                       ref_lengths: torch.Tensor) -> torch.Tensor:
+    """Edit counts of token ids already on the device, e.g. decoded tokens against padded targets in an
+    evaluation loop: (P, Lh) and (P, Lr) integer ids with (P,) lengths -> (P, 3) int32 (S, D, I) on the
+    device, no host round trip."""
+    def i32(t):
+        return t if t.dtype == torch.int32 else t.to(torch.int32)
+    return ops.edit_counts(i32(hyp_tokens), i32(ref_tokens), i32(hyp_lengths).contiguous(), i32(ref_lengths).contiguous())
