@@ -684,6 +684,40 @@ int vasr_ctc_beam_search_lm(const float* logits, int64_t ld_row, int64_t ld_utt,
                             int64_t ld_lm, double lm_weight, int32_t* trie, int32_t* out_tokens,
                             int32_t* out_len, double* out_score, int32_t* out_nbeams, void* stream);
 
+/* Per-frame shortlist for vasr_ctc_beam_search_shortlist, one launch for all B * L
+ * rows.  logits, ld_row, ld_utt, frames as vasr_ctc_beam_search_lm; V up to 2^20 (the row is staged
+ * in LDS up to V = 16384 and re-read from global memory above).  Each row's log-probabilities are
+ * bitwise those vasr_ctc_beam_search forms: the same operations and the same summation order.
+ * 1 <= K <= 64 (V >= 2; K above V - 1 is taken as V - 1, which then is the arrays' last extent):
+ *   out_tok, out_lp (B, L, K): the K non-blank tokens with the largest log-probabilities, ordered by
+ *   (log-probability descending, token ascending), and those log-probabilities; out_blank_lp (B, L):
+ *   the blank's.  Rows at or past min(max(frames[b], 0), L) are not read; they are filled with token
+ *   -1 and -inf.
+ * K == 0 (complete mode): out_lp (B, L, V) receives the whole log-probability rows, out_tok and
+ *   out_blank_lp are not used (may be NULL), and rows at or past the count are left unwritten. */
+int vasr_ctc_beam_shortlist_f32(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                                int K, int blank, const int32_t* frames, int32_t* out_tok, float* out_lp,
+                                float* out_blank_lp, void* stream);
+
+/* vasr_ctc_beam_search's frame step (lm_scorer = None) over the blank and each frame's K shortlisted
+ * tokens: nb * (K + 1) candidates per frame instead of nb * V, one wave per utterance.  tok, lp
+ * (B, L, K) and blank_lp (B, L) contiguous, as vasr_ctc_beam_shortlist_f32 writes them (1 <= K <=
+ * min(64, V - 1)); V is the vocabulary the tokens come from (insertion positions are those of the
+ * full search); W, blank, frames, trie and the four outputs as vasr_ctc_beam_search_lm.
+ * out_uncertified (B): the number of frames of utterance b whose step is not proved equal to the
+ * full search's.  A frame is certified when K == V - 1, or when it yields W survivors and the W-th
+ * survivor's score is strictly above s_i + (double)theta for every live beam score s_i, theta the
+ * shortlist's smallest log-probability (a comparison with NaN fails).  With out_uncertified[b] == 0
+ * utterance b's outputs are bitwise vasr_ctc_beam_search_lm's on the same logits; otherwise they
+ * are the pruned search's and the caller searches b again.
+ * tok == NULL (complete): lp is (B, L, V) log-probabilities (vasr_ctc_beam_shortlist_f32 with K = 0),
+ * looked up by token; K and blank_lp are ignored, no certificate is evaluated, out_uncertified is
+ * 0, and the result is vasr_ctc_beam_search_lm's for any V up to 2^20. */
+int vasr_ctc_beam_search_shortlist(const int32_t* tok, const float* lp, const float* blank_lp, int B, int L,
+                                   int K, int V, int W, int blank, const int32_t* frames, int32_t* trie,
+                                   int32_t* out_tokens, int32_t* out_len, double* out_score,
+                                   int32_t* out_nbeams, int32_t* out_uncertified, void* stream);
+
 /* Greedy CTC collapse per utterance (decode.py:51-69, :89-123): drop blank (and reset
  * prev), skip repeats of prev if collapse != 0.  out_tokens (B, L) holds each
  * utterance's kept tokens left-aligned, out_len (B) their counts.  If out_start /

@@ -213,9 +213,65 @@ class BigramLM:
             return cls(z["table"])
 
 
+def beam_shortlist_size(shortlist, vocab_size: int, beam_width: int) -> int:
+    """The K of a `shortlist=` argument: an int (1..64), or "auto" = max(16, 2 * beam_width); never
+    above vocab_size - 1, where the shortlist is every non-blank token."""
+    if isinstance(shortlist, str):
+        if shortlist != "auto":
+            raise ValueError(f'shortlist must be None, "auto" or an int, got {shortlist!r}')
+        K = max(16, 2 * int(beam_width))
+    else:
+        K = int(shortlist)
+    if not 1 <= K <= ops.BEAM_SHORTLIST_MAX:
+        raise ValueError(f"shortlist must lie in 1..{ops.BEAM_SHORTLIST_MAX}, got {K}")
+    return min(K, int(vocab_size) - 1)
+
+
+def _beam_search_exact(logits: torch.Tensor, beam_width: int, blank: int, frames):
+    """The full search (every token a candidate in every frame) of the utterances a shortlist did
+    not certify: the dense kernel where the vocabulary fits it, else complete log-probability rows
+    and the shortlist kernel's complete instance."""
+    V = logits.shape[-1]
+    if V <= ops.BEAM_DENSE_MAX_VOCAB:
+        return ops.ctc_beam_search(logits, beam_width, blank, frames=frames)
+    rows = ops.ctc_beam_shortlist(logits, 0, blank, frames)
+    return ops.ctc_beam_search_shortlist(None, rows, None, V, beam_width, blank, frames)[:4]
+
+
+def _beam_search_from_shortlist(short, vocab_size: int, beam_width: int, blank: int, frames, exact_of):
+    """One search launch over a batch's shortlist arrays `short` = ops.ctc_beam_shortlist's three,
+    then the exact search of the utterances with an uncertified frame: exact_of(indices, their
+    frames) gives _beam_search_exact's tensors for them.  Returns ops.ctc_beam_search's four
+    tensors: bitwise the full search's, by the certificate where it holds and by the second search
+    where it does not."""
+    toks, lens, scores, nb, unc = ops.ctc_beam_search_shortlist(*short, vocab_size, beam_width, blank, frames)
+    bad = torch.nonzero(unc.cpu()).flatten().tolist()
+    if bad:
+        idx = torch.tensor(bad, device=toks.device)
+        exact = exact_of(bad, None if frames is None else frames[idx])
+        for dst, src in zip((toks, lens, scores, nb), exact):
+            dst[idx] = src
+    return toks, lens, scores, nb
+
+
+def _beam_results(toks, lens, scores, nb) -> List[List[DecodingResult]]:
+    toks, lens, scores, nb = toks.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy(), nb.cpu().numpy()
+    return [[DecodingResult(text="", tokens=toks[b, r, :lens[b, r]].tolist(), score=float(scores[b, r]))
+             for r in range(int(nb[b]))] for b in range(toks.shape[0])]
+
+
+def _check_shortlist(who: str, shortlist, beam_width: int, lm_on: bool) -> None:
+    if lm_on:
+        raise ValueError(f"{who}: shortlist cannot be combined with a language model: with lm_weight > 0 a "
+                         "candidate outside the acoustic shortlist can win on its language-model term, so the "
+                         "per-frame certificate does not hold (DESIGN.md §3.6f); pass shortlist=None")
+    if not 1 <= beam_width <= 32:
+        raise ValueError(f"{who}: shortlist needs a beam width of 1..32, got {beam_width}")
+
+
 def ctc_beam_search(logits: torch.Tensor, beam_width: int = 10, blank_token: int = BLANK_TOKEN,
                     lm_weight: float = 0.0, lm_scorer: Optional[Any] = None,
-                    input_lengths=None) -> List[List[DecodingResult]]:
+                    input_lengths=None, shortlist=None) -> List[List[DecodingResult]]:
     """Prefix beam search (reference decode.py:128-217) on the HIP device.
 
     For widths 1..32 the whole search runs in one launch, one workgroup per utterance, prefixes
@@ -230,16 +286,29 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int = 10, blank_token: int
     Any other lm_scorer is a Python object the device cannot call, so with one (and lm_weight > 0),
     or with beam_width > 32, the search runs on the host with the same bookkeeping over
     device-computed log-probabilities -- one score() call per (beam, token, frame).
+
+    shortlist (extension): None is the search above.  An int K (1..64) or "auto"
+    (max(16, 2 * beam_width)) first reduces every frame to its K most probable non-blank tokens
+    (vasr_ctc_beam_shortlist_f32, one launch for all frames) and searches those
+    (vasr_ctc_beam_search_shortlist), which proves frame by frame that no other token could have
+    reached the beam; an utterance with a frame it cannot prove is searched again in full, so the
+    result is bitwise that of shortlist=None -- faster, and open to vocabularies above 16384, which
+    shortlist=None refuses.  Not with an active language model (ValueError), nor above width 32.
     """
     logits = _on_device(logits)
     lm_on = lm_scorer is not None and lm_weight > 0
+    if shortlist is not None and logits.dim() == 3 and logits.shape[-1] >= 2:
+        _check_shortlist("ctc_beam_search", shortlist, beam_width, lm_on)
+        x = logits.float()
+        B, L, V = x.shape
+        frames = ops._beam_frames("ctc_beam_search", input_lengths, B, L, x.device)
+        short = ops.ctc_beam_shortlist(x, beam_shortlist_size(shortlist, V, beam_width), blank_token, frames)
+        return _beam_results(*_beam_search_from_shortlist(
+            short, V, beam_width, blank_token, frames, lambda bad, fr: _beam_search_exact(x[bad], beam_width, blank_token, fr)))
     if (not lm_on or isinstance(lm_scorer, BigramLM)) and 1 <= beam_width <= 32:
         table = lm_scorer.device_table(logits.device) if lm_on else None
-        toks, lens, scores, nb = ops.ctc_beam_search(logits.float(), beam_width, blank_token, frames=input_lengths,
-                                                     lm_table=table, lm_weight=float(lm_weight) if lm_on else 0.0)
-        toks, lens, scores, nb = toks.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy(), nb.cpu().numpy()
-        return [[DecodingResult(text="", tokens=toks[b, r, :lens[b, r]].tolist(), score=float(scores[b, r]))
-                 for r in range(int(nb[b]))] for b in range(toks.shape[0])]
+        return _beam_results(*ops.ctc_beam_search(logits.float(), beam_width, blank_token, frames=input_lengths,
+                                                  lm_table=table, lm_weight=float(lm_weight) if lm_on else 0.0))
     return _ctc_beam_search_host(logits, beam_width, blank_token, lm_weight, lm_scorer, input_lengths)
 
 
@@ -348,9 +417,14 @@ class CTCDecoder:
                                timestamps=r.timestamps) for r in scored]
 
     def decode_beam_search(self, logits: torch.Tensor, beam_width: int = 10, return_all_beams: bool = False, *,
-                           input_lengths=None, lm_scorer: Optional[Any] = None, lm_weight: float = 0.0):
+                           input_lengths=None, lm_scorer: Optional[Any] = None, lm_weight: float = 0.0, shortlist=None):
         beam_results = ctc_beam_search(logits, beam_width=beam_width, blank_token=self.blank_token,
-                                       lm_weight=lm_weight, lm_scorer=lm_scorer, input_lengths=input_lengths)
+                                       lm_weight=lm_weight, lm_scorer=lm_scorer, input_lengths=input_lengths,
+                                       shortlist=shortlist)
+        return self._beam_texts(beam_results, return_all_beams)
+
+    def _beam_texts(self, beam_results, return_all_beams: bool):
+        """ctc_beam_search's results as decode_beam_search returns them."""
         if return_all_beams:
             for batch_results in beam_results:
                 for result in batch_results:

@@ -173,6 +173,54 @@ class CTCOutputHead(nn.Module):
             pred, lp = ops.argmax_logp(self.forward(x, normalized=normalized))
             return ops.ctc_collapse_conf(pred, lp, blank, frames=rows)
 
+    def beam_search(self, x: torch.Tensor, beam_width: int, blank: int = 0, rows=None, shortlist="auto",
+                    chunk_bytes: int = 256 << 20, normalized: bool = False):
+        """decode.ctc_beam_search(forward(x), beam_width, blank, input_lengths=rows, shortlist=shortlist)
+        without the (B, L, V) logits (extension): per utterance its beams as
+        DecodingResults, bitwise those.  The logits exist a chunk of whole utterances at a time
+        (rows * V * 4 <= chunk_bytes, at least one utterance; sizes come from shapes, never from
+        lengths), formed by the head's own GEMM into one reused buffer and reduced at once to each
+        frame's shortlist (ops.ctc_beam_shortlist) in the batch's (B, L, K) arrays; one search launch
+        then covers the batch, and an utterance with an uncertified frame has its own logits formed
+        again for the exact search.  shortlist: "auto" or 1..64.  A bf16 or QAT head, a one-token
+        vocabulary and shortlist=None go through forward()."""
+        from . import decode as dec
+
+        B, L, D = x.shape
+        W = int(beam_width)
+        lin = self.proj[2]
+        with torch.no_grad():
+            if shortlist is None or not self.fusable() or lin.weight.shape[0] < 2:
+                return dec.ctc_beam_search(self.forward(x, normalized=normalized), W, blank, input_lengths=rows,
+                                           shortlist=shortlist)
+            if int(chunk_bytes) <= 0:
+                raise ValueError("CTCOutputHead.beam_search: chunk_bytes must be positive")
+            dec._check_shortlist("CTCOutputHead.beam_search", shortlist, W, False)
+            V = lin.weight.shape[0]
+            K = dec.beam_shortlist_size(shortlist, V, W)
+            frames = ops._beam_frames("CTCOutputHead.beam_search", rows, B, L, x.device)
+            xn = ops._ln_prologue(x.reshape(B * L, D), self._ln(normalized))
+            nb = min(B, max(1, int(chunk_bytes) // max(L * V * 4, 1)))
+            buf = torch.empty((nb * L, V), device=x.device, dtype=torch.float32)
+
+            def logits_of(b0: int, b1: int) -> torch.Tensor:
+                return ops.gemm(xn[b0 * L:b1 * L], lin.weight, lin.bias, out=buf[:(b1 - b0) * L]).view(b1 - b0, L, V)
+
+            short = (torch.empty((B, L, K), device=x.device, dtype=torch.int32),
+                     torch.empty((B, L, K), device=x.device, dtype=torch.float32),
+                     torch.empty((B, L), device=x.device, dtype=torch.float32))
+            for b0 in range(0, B, nb):
+                b1 = min(b0 + nb, B)
+                ops.ctc_beam_shortlist(logits_of(b0, b1), K, blank, None if frames is None else frames[b0:b1],
+                                       out=tuple(t[b0:b1] for t in short))
+
+            def again(bad, fr):  # an uncertified utterance's own logits, in the same buffer, one at a time
+                parts = [dec._beam_search_exact(logits_of(b, b + 1), W, blank, None if fr is None else fr[i:i + 1])
+                         for i, b in enumerate(bad)]
+                return tuple(torch.cat(p) for p in zip(*parts))
+
+            return dec._beam_results(*dec._beam_search_from_shortlist(short, V, W, blank, frames, again))
+
     def fusable(self) -> bool:
         """Whether the loss can run straight from the head's input (ops.ctc_head_emissions): a plain
         fp32 nn.Linear.  A bf16 or QAT head goes through its logits."""
@@ -344,6 +392,21 @@ class VELOCITYASR(nn.Module):
         with torch.no_grad():
             _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
             return self.ctc_head.greedy_scored(x, blank, rows=rows, normalized=normalized)
+
+    def beam_search(self, mel_spectrogram: torch.Tensor, frames=None, beam_width: int = 10, blank: int = 0,
+                    shortlist="auto", chunk_bytes: int = 256 << 20):
+        """decode.ctc_beam_search(forward(mel, frames=frames), beam_width, blank, input_lengths=token rows,
+        shortlist=shortlist) without the (B, L, V) logits (CTCOutputHead.beam_search): per utterance
+        its beams as DecodingResults, bitwise those.  frames: per-utterance mel frame counts of a
+        zero-padded batch, as forward() takes them."""
+        if mel_spectrogram.device.type != "cuda":
+            _lib.require_device()
+            raise RuntimeError("velocity_asr (MI355X build): beam_search needs HIP tensors")
+        lengths = self._token_lengths(frames, mel_spectrogram.shape[1])
+        with torch.no_grad():
+            _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
+            return self.ctc_head.beam_search(x, beam_width, blank, rows=lengths, shortlist=shortlist,
+                                             chunk_bytes=chunk_bytes, normalized=normalized)
 
     def ctc_loss(self, mel_spectrogram: torch.Tensor, targets: torch.Tensor, input_lengths, target_lengths, *,
                  reduction: str = "mean", zero_infinity: bool = True, frames=None, blank: int = 0) -> torch.Tensor:

@@ -1308,13 +1308,8 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0, *, fr
     B, Lq, V = x.shape
     W = int(beam_width)
     dev = x.device
-    fr = tab = None
-    if frames is not None:
-        if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
-            host = torch.as_tensor(frames)
-            if host.numel() and not host.dtype.is_floating_point and (int(host.min()) < 0 or int(host.max()) > Lq):
-                raise ValueError(f"ctc_beam_search.frames: counts must lie in 0..{Lq}, got {host.tolist()}")
-        fr = _ctc_lengths("ctc_beam_search.frames", frames, B, dev, Lq)
+    tab = None
+    fr = _beam_frames("ctc_beam_search", frames, B, Lq, dev)
     if lm_table is not None:
         _cuda_f32("ctc_beam_search.lm_table", lm_table)
         if tuple(lm_table.shape) != (V + 1, V):
@@ -1335,6 +1330,103 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0, *, fr
                                               trie.data_ptr(), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
                                               nbeams.data_ptr(), stream_of(x)), "vasr_ctc_beam_search_lm")
     return toks, lens, scores, nbeams
+
+
+BEAM_SHORTLIST_MAX = 64  # tokens per frame of a shortlist (csrc/beam_shortlist.hip)
+BEAM_DENSE_MAX_VOCAB = 16384  # vasr_ctc_beam_search[_lm]: the row's log-probabilities live in LDS
+
+
+def _beam_frames(who: str, frames, B: int, Lq: int, device) -> Optional[torch.Tensor]:
+    """ctc_beam_search's frames rule: a host sequence must lie in 0..L, a device tensor is taken as
+    it is (the kernels clamp it)."""
+    if frames is None:
+        return None
+    if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
+        host = torch.as_tensor(frames)
+        if host.numel() and not host.dtype.is_floating_point and (int(host.min()) < 0 or int(host.max()) > Lq):
+            raise ValueError(f"{who}.frames: counts must lie in 0..{Lq}, got {host.tolist()}")
+    return _ctc_lengths(f"{who}.frames", frames, B, device, Lq)
+
+
+def ctc_beam_shortlist(logits: torch.Tensor, K: int, blank: int = 0, frames=None, out=None):
+    """Per-frame shortlist of (B, L, V) logits (vasr_ctc_beam_shortlist_f32) ->
+    (tokens (B, L, K) int32, log-probabilities (B, L, K), blank log-probabilities (B, L)): each
+    frame's K non-blank tokens of largest log-probability, ordered by (log-probability descending,
+    token ascending); the log-probabilities are bitwise those ctc_beam_search forms.  K is 1..64 and
+    is clamped to V - 1.  frames as ctc_beam_search; rows past a count are not read and hold token
+    -1 and -inf.  out: the three tensors to write into (an utterance slice of a batch's arrays).
+    K = 0 (complete mode) returns the whole (B, L, V) log-probability rows instead, rows past a
+    count unwritten."""
+    _cuda_f32("ctc_beam_shortlist.logits", logits)
+    if logits.dim() != 3:
+        raise ValueError("ctc_beam_shortlist: logits must be (B, L, V)")
+    x = logits if logits.stride(-1) == 1 else logits.contiguous()
+    B, Lq, V = x.shape
+    K = int(K)
+    if not 0 <= K <= BEAM_SHORTLIST_MAX:
+        raise ValueError(f"ctc_beam_shortlist: K must be 1..{BEAM_SHORTLIST_MAX} (or 0: complete rows), got {K}")
+    if K and V < 2:
+        raise ValueError("ctc_beam_shortlist: a shortlist needs a non-blank token (V >= 2)")
+    dev = x.device
+    fr = _beam_frames("ctc_beam_shortlist", frames, B, Lq, dev)
+    if K == 0:
+        full = torch.empty((B, Lq, V), device=dev, dtype=torch.float32)
+        check(L.lib().vasr_ctc_beam_shortlist_f32(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, 0, int(blank), ptr(fr),
+                                                  None, full.data_ptr(), None, stream_of(x)), "vasr_ctc_beam_shortlist_f32")
+        return full
+    K = min(K, V - 1)
+    if out is None:
+        out = (torch.empty((B, Lq, K), device=dev, dtype=torch.int32),
+               torch.empty((B, Lq, K), device=dev, dtype=torch.float32),
+               torch.empty((B, Lq), device=dev, dtype=torch.float32))
+    tok, lp, bl = out
+    for n, t, dt, shape in (("tokens", tok, torch.int32, (B, Lq, K)), ("log-probabilities", lp, torch.float32, (B, Lq, K)),
+                            ("blank log-probabilities", bl, torch.float32, (B, Lq))):
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"ctc_beam_shortlist: out {n} must be a contiguous {dt} {shape} tensor on {dev}")
+    check(L.lib().vasr_ctc_beam_shortlist_f32(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, K, int(blank), ptr(fr),
+                                              tok.data_ptr(), lp.data_ptr(), bl.data_ptr(), stream_of(x)),
+          "vasr_ctc_beam_shortlist_f32")
+    return tok, lp, bl
+
+
+def ctc_beam_search_shortlist(tok: Optional[torch.Tensor], lp: torch.Tensor, blank_lp: Optional[torch.Tensor], V: int,
+                              beam_width: int, blank: int = 0, frames=None):
+    """Prefix beam search over ctc_beam_shortlist's arrays (vasr_ctc_beam_search_shortlist) ->
+    (tokens (B, W, L) int32, lengths (B, W), scores (B, W) float64, beams per utterance (B,),
+    uncertified frames per utterance (B,)), all on the device.  Where uncertified[b] is 0, utterance
+    b's results are bitwise ctc_beam_search's on the logits the shortlist came from; elsewhere they
+    are not proved to be, and the caller searches b again.  V: the vocabulary size.  tok = None
+    (complete): lp is the (B, L, V) rows of ctc_beam_shortlist(K=0) and the search is the exact one,
+    for any V."""
+    _cuda_f32("ctc_beam_search_shortlist.lp", lp)
+    if lp.dim() != 3 or not lp.is_contiguous():
+        raise ValueError("ctc_beam_search_shortlist: lp must be a contiguous (B, L, K) tensor")
+    B, Lq, K = lp.shape
+    V, W, dev = int(V), int(beam_width), lp.device
+    if tok is None:
+        if K != V:
+            raise ValueError(f"ctc_beam_search_shortlist: complete rows must be (B, L, {V}), got {tuple(lp.shape)}")
+    else:
+        _cuda_f32("ctc_beam_search_shortlist.blank_lp", blank_lp)
+        if (tok.device != dev or tok.dtype != torch.int32 or tok.shape != lp.shape or not tok.is_contiguous()
+                or tuple(blank_lp.shape) != (B, Lq) or not blank_lp.is_contiguous()):
+            raise ValueError("ctc_beam_search_shortlist: tok must be int32 (B, L, K) and blank_lp (B, L), contiguous, "
+                             "beside lp")
+        if not 1 <= K <= min(BEAM_SHORTLIST_MAX, V - 1):
+            raise ValueError(f"ctc_beam_search_shortlist: K = {K} outside 1..{min(BEAM_SHORTLIST_MAX, V - 1)} for V = {V}")
+    fr = _beam_frames("ctc_beam_search_shortlist", frames, B, Lq, dev)
+    trie = torch.empty(max(B, 1) * int(L.lib().vasr_ctc_beam_workspace_elems(Lq, W)), device=dev, dtype=torch.int32)
+    toks = torch.zeros((B, W, max(Lq, 1)), device=dev, dtype=torch.int32)
+    lens = torch.zeros((B, W), device=dev, dtype=torch.int32)
+    scores = torch.zeros((B, W), device=dev, dtype=torch.float64)
+    nbeams = torch.zeros((B,), device=dev, dtype=torch.int32)
+    unc = torch.zeros((B,), device=dev, dtype=torch.int32)
+    check(L.lib().vasr_ctc_beam_search_shortlist(ptr(tok), lp.data_ptr(), ptr(blank_lp), B, Lq, 0 if tok is None else K, V,
+                                                 W, int(blank), ptr(fr), trie.data_ptr(), toks.data_ptr(), lens.data_ptr(),
+                                                 scores.data_ptr(), nbeams.data_ptr(), unc.data_ptr(), stream_of(lp)),
+          "vasr_ctc_beam_search_shortlist")
+    return toks, lens, scores, nbeams, unc
 
 
 def _ctc_lengths(name: str, t, B: int, device, default: int) -> torch.Tensor:

@@ -94,7 +94,9 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
                   lm_weight: float = 0.0, confidence: bool = False, raw: bool = False) -> List:
     """(b, S) device audio -> [(text, words or None)] through the device pipeline.  lengths:
     per-clip sample counts when the clips were zero-padded to S.  lm / lm_weight: language model
-    for the beam search (decode.BigramLM runs on the device).  confidence (greedy only):
+    for the beam search (decode.BigramLM runs on the device).  VASR_BEAM_SHORTLIST=1 (read per call)
+    sends a beam search without an active language model through model.beam_search: the same beams
+    from per-frame shortlists, without the (B, L, V) logits.  confidence (greedy only):
     [(text, words with "confidence", path log-probability)] from model.greedy_scored.
     raw: per clip the integer arrays instead of text (a dict as stitch_segments takes and _render
     turns into the tuple above): what the segments of a long recording are stitched from."""
@@ -102,6 +104,13 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
         mel = mel_on_device(audio, n_mels=model.config.mel_bins, lengths=lengths,
                             frame_pad=model.temporal_binding.conv_padding())
         frames = None if lengths is None else [n // HOP_LENGTH + 1 for n in lengths]
+        if 1 < beam_width <= 32 and not (lm is not None and lm_weight > 0) \
+                and os.environ.get("VASR_BEAM_SHORTLIST", "0") == "1":
+            # the same beams without the (B, L, V) logits: per-frame shortlists, then one search launch
+            beams = model.beam_search(mel, frames=frames, beam_width=beam_width, blank=decoder.blank_token)
+            if raw:
+                return [{"tokens": list(r[0].tokens) if r else []} for r in beams]
+            return [(t, None) for t in decoder._beam_texts(beams, False)]
         if beam_width > 1:
             logits = model(mel, frames=frames)
             # one search launch for the batch: each clip's workgroup stops at its own row count
