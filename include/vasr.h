@@ -508,6 +508,38 @@ int64_t vasr_edit_workspace_bytes(int P, int max_hyp, int max_ref);
 int vasr_edit_wave_cols(void);
 int vasr_edit_tile_cols(void);
 
+/* ------------------------------------------------------------------ WER / CER alignment (device)
+ * The edit path behind the counts above, the rule velocity_asr.training.edit_alignment_host states:
+ * cell (0, j > 0) is a deletion, cell (i > 0, 0) an insertion, hyp[i-1] == ref[j-1] a hit, otherwise
+ * the smallest of c[i-1][j-1], c[i][j-1], c[i-1][j], ties to the first of substitution, deletion,
+ * insertion; the path walks back from (hyp_len, ref_len) along those choices.  Operation codes:
+ * 0 hit, 1 substitution, 2 deletion (a reference item with no counterpart), 3 insertion (a hypothesis
+ * item with no counterpart).
+ * vasr_edit_align_i32: the arguments up to `counts` are vasr_edit_counts_i32's, with the same limits,
+ *   and counts receives the same integers.  The same two sweeps also keep each cell's choice, 2 bits,
+ *   eight columns to a 16-bit word, in the pair's part of `table`; a third kernel walks the choices
+ *   back with one wave per pair and writes ops[p*ld_ops + k], k < ops_len[p] = ref_len + I, in
+ *   forward order (I is in the counts by then, so nothing is reversed).  Nothing is written in ops[p]
+ *   at or past ops_len[p]; ld_ops >= max_hyp + max_ref.
+ *   Table.  Pair p of m x n clamped items uses vasr_edit_align_table_bytes(m, n) =
+ *   2 * m * ceil(n / 8) bytes from table + table_offset[p] (device int64, (P,)).  The word of row i,
+ *   strip s lies at ((i - 1 + s) mod m) * ceil(n / 8) + s: a sweep's wave stores one step's words side
+ *   by side.  The kernels work the extent out from the device lengths themselves; a pair whose offset
+ *   is negative or odd, or whose offset + extent exceeds table_bytes, is skipped: ops_len[p] = -1, its
+ *   counts are still written, and neither the table nor ops is touched for it.  `table` is not NULL
+ *   and 2-byte aligned; it is written before it is read.  (Environment VASR_EDIT_ALIGN_STAGE=1 runs
+ *   the sweeps only, =2 the walk only over what an earlier call left in the same buffers: a timing aid.)
+ * vasr_edit_align_table_bytes: one pair's extent; -1 for a length outside 0..65535.
+ * workspace: as vasr_edit_workspace_bytes(P, max_hyp, max_ref) states.  All arrays are on the device.
+ * Integer only, no atomics.  No allocation, no synchronisation, no host read; everything is enqueued
+ * on `stream`.  Argument errors return VASR_EINVAL before any device call. */
+int vasr_edit_align_i32(const int32_t* hyp, int64_t ld_hyp, const int32_t* hyp_len, int max_hyp,
+                        const int32_t* ref, int64_t ld_ref, const int32_t* ref_len, int max_ref, int P,
+                        int32_t* counts, uint8_t* ops, int64_t ld_ops, int32_t* ops_len,
+                        const int64_t* table_offset, void* table, int64_t table_bytes, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+int64_t vasr_edit_align_table_bytes(int hyp_len, int ref_len);
+
 /* ------------------------------------------------------------------ mel front end
  * compute_mel_spectrogram (audio.py:65-143) is three launches:
  *  1. vasr_reflect_pad_f32: xp[b][0:S+2*pad] = reflect-padded audio (audio.py:100-101),

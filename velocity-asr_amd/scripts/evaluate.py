@@ -11,6 +11,8 @@ dataset loader is a stub that loads nothing. --beam-width > 1 selects prefix bea
 launch per batch; --lm FILE.npz --lm-weight X fuses a bigram table (decode.BigramLM.save) into it.
 WER and CER are scored on --device (one batched edit-distance launch per unit); --error-breakdown adds the
 substitution / deletion / insertion totals to the report, --per-utterance FILE writes them per file.
+--alignments FILE writes each file's word alignment (which word for which), --confusions N appends the most
+frequent word confusions to the report; the edit paths come from the device too (training.error_alignments).
 """
 
 import argparse
@@ -24,7 +26,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from velocity_asr import VELOCITYASR, CTCDecoder, create_default_vocabulary  # noqa: E402
 from velocity_asr.decode import BigramLM  # noqa: E402
-from velocity_asr.training import error_counts, error_rate  # noqa: E402
+from velocity_asr.training import confusions, error_alignments, error_counts, error_rate, format_alignment  # noqa: E402
 from velocity_asr.transcription import find_audio_files, load_manifest, transcribe_files  # noqa: E402
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s | %(levelname)s | %(message)s",
@@ -53,6 +55,10 @@ def parse_args(argv=None):
                    help="With --test-set: append the word and character substitution/deletion/insertion totals")
     p.add_argument("--per-utterance", default=None, metavar="FILE",
                    help="With --test-set: write one TSV row per scored file (path, reference words, word S, D, I, WER)")
+    p.add_argument("--alignments", default=None, metavar="FILE",
+                   help="With --test-set: write every scored file's word alignment (path, counts, REF/HYP view)")
+    p.add_argument("--confusions", type=int, default=0, metavar="N",
+                   help="With --test-set: append the N most frequent word substitutions, deletions and insertions")
     args = p.parse_args(argv)
     if args.test_set is None and args.audio_dir is None:
         p.error("Either --test-set or --audio-dir must be specified")
@@ -131,6 +137,22 @@ def main(argv=None) -> int:
             for path, c in zip(paths, words):
                 f.write(f"{path}\t{c.ref_length}\t{c.substitutions}\t{c.deletions}\t{c.insertions}\t{c.rate:.6f}\n")
         logger.info(f"Per-utterance counts saved to {args.per_utterance}")
+    if args.alignments or args.confusions > 0:
+        aligned = error_alignments(preds, refs, "word", score_device)  # the edit paths, walked back on the device
+        if args.confusions > 0:
+            sub, dele, ins = confusions(aligned)
+            for name, counter, show in (("substitutions", sub, lambda k: f"{k[0]} -> {k[1]}"),
+                                        ("deletions", dele, str), ("insertions", ins, str)):
+                report.append(f"Top word {name}:")
+                # most frequent first, equal counts in the order of first appearance
+                report += [f"  {n:6d}  {show(k)}" for k, n in counter.most_common(args.confusions)]
+        if args.alignments:
+            with open(args.alignments, "w", encoding="utf-8") as f:
+                for path, al in zip(paths, aligned):
+                    c = al.counts
+                    f.write(f"{path}\tN={c.ref_length} S={c.substitutions} D={c.deletions} I={c.insertions}\n"
+                            f"{format_alignment(al)}\n\n")
+            logger.info(f"Alignments saved to {args.alignments}")
     print("\n" + RULE)
     print("EVALUATION RESULTS")
     print(RULE)

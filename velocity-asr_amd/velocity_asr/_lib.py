@@ -118,6 +118,9 @@ _SIGNATURES = {
     "vasr_edit_workspace_bytes": ([ctypes.c_int] * 3, c_i64),
     "vasr_edit_wave_cols": ([], ctypes.c_int),
     "vasr_edit_tile_cols": ([], ctypes.c_int),
+    "vasr_edit_align_i32": ([c_p, c_i64, c_p, ctypes.c_int, c_p, c_i64, c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, c_i64,
+                             c_p, c_p, c_p, c_i64, c_p, c_i64, c_p], ctypes.c_int),
+    "vasr_edit_align_table_bytes": ([ctypes.c_int] * 2, c_i64),
     "vasr_reflect_pad_f32": ([c_p, c_i64, c_p, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p], ctypes.c_int),
     "vasr_mel_log_norm_f32": ([c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p],
                               ctypes.c_int),

@@ -1008,6 +1008,91 @@ def edit_counts(hyp: torch.Tensor, ref: torch.Tensor, hyp_lengths: torch.Tensor,
     return counts
 
 
+# Default budget of edit_alignment's choice table per launch.  A pair's table is 2 * hyp_len * ceil(ref_len / 8)
+# bytes (20 MB for 9000 x 9000, 1.07 GB for 65535 x 65535), so 1 GiB holds every pair but the very largest.
+EDIT_ALIGN_TABLE_BYTES = 1 << 30
+_EDIT_TABLE_ALIGN = 16  # the pairs' offsets inside the table
+
+
+def _host_lens(name: str, t, P: int, width: int, device):
+    """Lengths as a host sequence or a device tensor -> (contiguous int32 device tensor, clamped host list)."""
+    if isinstance(t, torch.Tensor):
+        dev = _lens(name, t, P, device)
+        host = dev.cpu().tolist()
+    else:
+        host = [int(x) for x in t]
+        if len(host) != P:
+            raise ValueError(f"{name}: expected {P} lengths, got {len(host)}")
+        dev = torch.tensor(host, dtype=torch.int32).to(device)
+    return dev, [min(max(x, 0), width) for x in host]
+
+
+def edit_alignment(hyp: torch.Tensor, ref: torch.Tensor, hyp_lengths, ref_lengths,
+                   table_bytes: int = EDIT_ALIGN_TABLE_BYTES):
+    """Edit paths of P pairs (vasr_edit_align_i32): hyp, ref as in edit_counts; the lengths are sequences of
+    ints when the host knows them, or int32 (P,) device tensors, which are then read back once (the caller is
+    about to download the paths anyway).  -> (counts (P, 3) int32, ops (P, max(1, Lh + Lr)) uint8, ops_len (P,)
+    int32), all on the device: ops[p, :ops_len[p]] are the codes of training.edit_alignment_host (0 hit,
+    1 substitution, 2 deletion, 3 insertion) and counts equals edit_counts'; ops past ops_len is unspecified.
+    The choice table is sized by the sum of the pairs' own extents (vasr_edit_align_table_bytes) and the pairs
+    are split into as many launches as fit `table_bytes` each (default EDIT_ALIGN_TABLE_BYTES, 1 GiB).  A single
+    pair whose own table exceeds table_bytes is not aligned: its ops_len is -1 (its counts are still right)
+    and the caller handles it."""
+    hyp, ld_h, mh = _id_rows("edit_alignment.hyp", hyp)
+    ref, ld_r, mr = _id_rows("edit_alignment.ref", ref)
+    P = hyp.shape[0]
+    if ref.shape[0] != P or ref.device != hyp.device:
+        raise ValueError(f"edit_alignment: hyp has {P} rows on {hyp.device}, ref {ref.shape[0]} on {ref.device}")
+    if hyp_lengths is None or ref_lengths is None:
+        raise ValueError("edit_alignment: hyp_lengths and ref_lengths are required")
+    table_bytes = int(table_bytes)
+    if table_bytes < 0:
+        raise ValueError(f"edit_alignment: table_bytes must not be negative, got {table_bytes}")
+    hyp_lengths, hl = _host_lens("edit_alignment.hyp_lengths", hyp_lengths, P, mh, hyp.device)
+    ref_lengths, rl = _host_lens("edit_alignment.ref_lengths", ref_lengths, P, mr, hyp.device)
+    lib = L.lib()
+    extent = [int(lib.vasr_edit_align_table_bytes(a, b)) for a, b in zip(hl, rl)]
+    # launches: runs [p0, p1) of consecutive pairs whose tables fit the budget together; offset -1 marks a
+    # pair that is over the budget alone, which ends a run and is left out
+    offsets, runs, p0, used = [], [], 0, 0
+    for p, e in enumerate(extent):
+        e = -(-e // _EDIT_TABLE_ALIGN) * _EDIT_TABLE_ALIGN
+        if e > table_bytes or used + e > table_bytes or p - p0 == EDIT_MAX_ITEMS:
+            if p > p0:
+                runs.append((p0, p, used))
+            p0, used = p, 0
+        if e > table_bytes:
+            offsets.append(-1)
+            p0 = p + 1
+            continue
+        offsets.append(used)
+        used += e
+    if P > p0:
+        runs.append((p0, P, used))
+    dev = hyp.device
+    ld_ops = max(1, mh + mr)
+    counts = torch.empty((P, 3), device=dev, dtype=torch.int32)
+    ops = torch.empty((P, ld_ops), device=dev, dtype=torch.uint8)
+    ops_len = torch.full((P,), -1, device=dev, dtype=torch.int32)
+    offs = torch.tensor(offsets, dtype=torch.int64).to(dev)
+    table = torch.empty((max([u for _, _, u in runs] + [_EDIT_TABLE_ALIGN]),), device=dev, dtype=torch.uint8)
+    stream = stream_of(hyp)
+    for p0, p1, used in runs:  # launches on one stream share the table: each writes its part before reading it
+        n = p1 - p0
+        need = int(lib.vasr_edit_workspace_bytes(n, mh, mr))
+        if need < 0:
+            raise ValueError(f"edit_alignment: sizes ({n}, {mh}, {mr}) outside the kernel's limits")
+        ws = torch.empty((need // 8,), device=dev, dtype=torch.int64) if need else None
+        check(lib.vasr_edit_align_i32(hyp[p0:].data_ptr(), ld_h, hyp_lengths[p0:].data_ptr(), mh, ref[p0:].data_ptr(), ld_r,
+                                      ref_lengths[p0:].data_ptr(), mr, n, counts[p0:].data_ptr(), ops[p0:].data_ptr(), ld_ops,
+                                      ops_len[p0:].data_ptr(), offs[p0:].data_ptr(), table.data_ptr(), used, ptr(ws), need,
+                                      stream), "vasr_edit_align_i32")
+    for p, o in enumerate(offsets):
+        if o < 0:  # over the budget alone: counts only
+            counts[p:p + 1] = edit_counts(hyp[p:p + 1], ref[p:p + 1], hyp_lengths[p:p + 1], ref_lengths[p:p + 1])
+    return counts, ops, ops_len
+
+
 def mel_log_norm(power: torch.Tensor, ld_power: int, stride_power: int, fb_csr, B: int, F: int, n_mels: int,
                  normalize: bool, frames: Optional[torch.Tensor] = None, frame_pad: int = 0) -> torch.Tensor:
     """frames: per-utterance frame counts (int32 (B,), each <= F); frames past them are 0.

@@ -32,6 +32,9 @@ The metrics: compute_wer / compute_cer are the reference's (a Python Levenshtein
 device, in which case error_counts scores all pairs in one launch of the batched edit-distance kernel
 (vasr_edit_counts_i32) and they return the same float.  edit_counts_host is that kernel's specification:
 substitution, deletion and insertion counts carried forward with the cost.
+error_alignments returns the edit paths behind those counts (which item for which), on a HIP device from
+vasr_edit_align_i32; edit_alignment_host is its specification, format_alignment and confusions read the
+paths.
 """
 
 from __future__ import annotations
@@ -430,6 +433,40 @@ def _is_hip(device) -> bool:
     return device is not None and torch.device(device).type == "cuda"
 
 
+def _item_pairs(what: str, predictions: List[str], references: List[str], unit: str):
+    """The (hypothesis items, reference items) of each pair: compute_wer's or compute_cer's normalisation."""
+    if unit not in ("word", "char"):
+        raise ValueError(f"{what}: unit must be 'word' or 'char', got {unit!r}")
+    split = (lambda s: s.lower().split()) if unit == "word" else (lambda s: list(s.lower()))
+    return [(split(p), split(r)) for p, r in zip(predictions, references)]
+
+
+def _device_pairs(pairs, device, min_cells: int) -> List[int]:
+    """Indices of the pairs a HIP device scores: all that fit the kernel, unless they are fewer than min_cells cells."""
+    if not _is_hip(device):
+        return []
+    on_device = [k for k, (h, r) in enumerate(pairs) if len(h) <= MAX_DEVICE_ITEMS and len(r) <= MAX_DEVICE_ITEMS]
+    if sum(len(pairs[k][0]) * len(pairs[k][1]) for k in on_device) < min_cells:
+        return []
+    return on_device
+
+
+def _interned(pairs, which: List[int]):
+    """One host buffer for one upload: [hyp ids | ref ids | hyp length | ref length] per chosen pair, the items
+    interned as int32 ids of one dictionary.  -> (buffer (P, mh + mr + 2), mh, mr)."""
+    import numpy as np
+    ids: dict = {}
+    mh = max(1, max(len(pairs[k][0]) for k in which))
+    mr = max(1, max(len(pairs[k][1]) for k in which))
+    buf = np.zeros((len(which), mh + mr + 2), np.int32)
+    for row, k in zip(buf, which):
+        h, r = pairs[k]
+        row[:len(h)] = [ids.setdefault(x, len(ids)) for x in h]
+        row[mh:mh + len(r)] = [ids.setdefault(x, len(ids)) for x in r]
+        row[mh + mr], row[mh + mr + 1] = len(h), len(r)
+    return buf, mh, mr
+
+
 def error_counts(predictions: List[str], references: List[str], unit: str = "word", device=None) -> List[ErrorCounts]:
     """Per-pair substitution / deletion / insertion counts.  The text normalisation is compute_wer's
     (unit "word": .lower().split()) or compute_cer's ("char": list(.lower())).  device None (or a
@@ -437,29 +474,11 @@ def error_counts(predictions: List[str], references: List[str], unit: str = "wor
     per call), uploads the padded id matrices and lengths once, runs vasr_edit_counts_i32 and downloads
     the (P, 3) counts once; a pair with a side longer than 65535 items is scored on the host in the
     same call, and so is a batch of fewer than MIN_DEVICE_CELLS cells."""
-    if unit not in ("word", "char"):
-        raise ValueError(f"error_counts: unit must be 'word' or 'char', got {unit!r}")
-    split = (lambda s: s.lower().split()) if unit == "word" else (lambda s: list(s.lower()))
-    pairs = [(split(p), split(r)) for p, r in zip(predictions, references)]
+    pairs = _item_pairs("error_counts", predictions, references, unit)
     out: List[ErrorCounts] = [None] * len(pairs)  # type: ignore[list-item]
-    on_device = []
-    if _is_hip(device):
-        on_device = [k for k, (h, r) in enumerate(pairs) if len(h) <= MAX_DEVICE_ITEMS and len(r) <= MAX_DEVICE_ITEMS]
-        if sum(len(pairs[k][0]) * len(pairs[k][1]) for k in on_device) < MIN_DEVICE_CELLS:
-            on_device = []
+    on_device = _device_pairs(pairs, device, MIN_DEVICE_CELLS)
     if on_device:
-        import numpy as np
-        ids: dict = {}
-        P = len(on_device)
-        mh = max(1, max(len(pairs[k][0]) for k in on_device))
-        mr = max(1, max(len(pairs[k][1]) for k in on_device))
-        # one host buffer, one upload: [hyp ids | ref ids | hyp lengths | ref lengths] per pair
-        buf = np.zeros((P, mh + mr + 2), np.int32)
-        for row, k in zip(buf, on_device):
-            h, r = pairs[k]
-            row[:len(h)] = [ids.setdefault(x, len(ids)) for x in h]
-            row[mh:mh + len(r)] = [ids.setdefault(x, len(ids)) for x in r]
-            row[mh + mr], row[mh + mr + 1] = len(h), len(r)
+        buf, mh, mr = _interned(pairs, on_device)
         dev = torch.from_numpy(buf).to(device)
         got = ops.edit_counts(dev[:, :mh], dev[:, mh:mh + mr], dev[:, mh + mr].contiguous(),
                               dev[:, mh + mr + 1].contiguous()).cpu().tolist()
@@ -480,3 +499,165 @@ def token_error_counts(hyp_tokens: torch.Tensor, hyp_lengths: torch.Tensor, ref_
     def i32(t):
         return t if t.dtype == torch.int32 else t.to(torch.int32)
     return ops.edit_counts(i32(hyp_tokens), i32(ref_tokens), i32(hyp_lengths).contiguous(), i32(ref_lengths).contiguous())
+
+
+# --------------------------------------------------------------------------- alignments
+HIT, SUBSTITUTION, DELETION, INSERTION = range(4)  # operation codes of an edit path
+
+
+def edit_alignment_host(hyp: Sequence, ref: Sequence) -> List[int]:
+    """The edit path of hyp against ref in forward order, one code per operation (0 hit, 1 substitution,
+    2 deletion: a reference item with no counterpart, 3 insertion: a hypothesis item with no counterpart):
+    the specification the device kernels (vasr_edit_align_i32) reproduce exactly.  Every cell of
+    edit_counts_host's DP gets one choice: cell (0, j > 0) deletion, cell (i > 0, 0) insertion,
+    hyp[i-1] == ref[j-1] hit, unconditionally; otherwise the smallest of c[i-1][j-1], c[i][j-1], c[i-1][j]
+    (c the cost S + D + I), ties to the first of substitution, deletion, insertion.  The path walks back from
+    (len(hyp), len(ref)) along the choices and is reversed.  Its counts are edit_counts_host's, and its length
+    is len(ref) + insertions."""
+    m, n = len(hyp), len(ref)
+    prev = list(range(n + 1))
+    choice = []  # choice[i - 1][j], i >= 1, j >= 1
+    for i in range(1, m + 1):
+        cur = [i] + [0] * n
+        ch = bytearray(n + 1)
+        hi = hyp[i - 1]
+        for j in range(1, n + 1):
+            if hi == ref[j - 1]:
+                cur[j] = prev[j - 1]
+                continue
+            best, cost = SUBSTITUTION, prev[j - 1]
+            if cur[j - 1] < cost:
+                best, cost = DELETION, cur[j - 1]
+            if prev[j] < cost:
+                best, cost = INSERTION, prev[j]
+            cur[j], ch[j] = cost + 1, best
+        choice.append(ch)
+        prev = cur
+    path = []
+    i, j = m, n
+    while i > 0 or j > 0:
+        op = DELETION if i == 0 else INSERTION if j == 0 else choice[i - 1][j]
+        path.append(op)
+        i -= op != DELETION
+        j -= op != INSERTION
+    path.reverse()
+    return path
+
+
+def _path_counts(path: Sequence[int]) -> Tuple[int, int, int]:
+    s = d = i = 0
+    for op in path:
+        s += op == SUBSTITUTION
+        d += op == DELETION
+        i += op == INSERTION
+    return s, d, i
+
+
+@dataclass
+class Alignment:
+    """One hypothesis aligned to its reference: the two item lists (words or characters, normalised as
+    compute_wer / compute_cer do), the path's operation codes in forward order and its counts."""
+
+    hyp: List
+    ref: List
+    ops: List[int]
+    counts: ErrorCounts
+
+    def pairs(self):
+        """Yields (op, hyp item or None, ref item or None, hyp index, ref index) along the path; the index
+        of a missing side is that of the next item on that side."""
+        i = j = 0
+        for op in self.ops:
+            yield (op, None if op == DELETION else self.hyp[i], None if op == INSERTION else self.ref[j], i, j)
+            i += op != DELETION
+            j += op != INSERTION
+
+
+# error_alignments(device=...) keeps a batch of fewer DP cells than this on the host: its device call also
+# downloads the paths and builds the objects, so it breaks even later than error_counts (profiles/align.md:
+# the host wins at 1770 cells, the device at 3597).
+ALIGN_MIN_DEVICE_CELLS = 2500
+ALIGN_TABLE_BYTES = ops.EDIT_ALIGN_TABLE_BYTES  # a pair whose choice table is larger is aligned on the host
+
+
+def _length_buckets(pairs, which: List[int]) -> List[List[int]]:
+    """`which` by rising size, cut where a pair is more than four times as long as its bucket's first (of at
+    least 64 items): every bucket is one padded upload, and a few long pairs must not widen all the rows."""
+    size = lambda k: len(pairs[k][0]) + len(pairs[k][1])  # noqa: E731
+    out: List[List[int]] = []
+    for k in sorted(which, key=size):
+        if out and size(k) <= 4 * max(64, size(out[-1][0])):
+            out[-1].append(k)
+        else:
+            out.append([k])
+    return out
+
+
+def error_alignments(predictions: List[str], references: List[str], unit: str = "word", device=None) -> List[Alignment]:
+    """Per-pair edit paths: which item was substituted for which, which were dropped and which added.  Text
+    normalisation and interning are error_counts'.  device None (or a non-HIP device) runs edit_alignment_host.
+    A HIP device runs vasr_edit_align_i32 (ops.edit_alignment), one upload and one download per bucket of pairs
+    of similar length; on the host stay a pair with a side longer than 65535 items or a choice table over
+    ALIGN_TABLE_BYTES, and a batch of fewer than ALIGN_MIN_DEVICE_CELLS cells.  The paths and counts are the
+    same either way."""
+    pairs = _item_pairs("error_alignments", predictions, references, unit)
+    paths: list = [None] * len(pairs)
+    on_device = _device_pairs(pairs, device, ALIGN_MIN_DEVICE_CELLS)
+    for bucket in _length_buckets(pairs, on_device):
+        buf, mh, mr = _interned(pairs, bucket)
+        dev = torch.from_numpy(buf).to(device)
+        _, path, length = ops.edit_alignment(dev[:, :mh], dev[:, mh:mh + mr], buf[:, mh + mr].tolist(),
+                                             buf[:, mh + mr + 1].tolist(), table_bytes=ALIGN_TABLE_BYTES)
+        length = length.cpu().tolist()
+        path = path[:, :max(1, max(length))].cpu().numpy()
+        for k, row, n in zip(bucket, path, length):
+            if n >= 0:
+                paths[k] = row[:n].tolist()
+    out = []
+    for (h, r), path in zip(pairs, paths):
+        if path is None:
+            path = edit_alignment_host(h, r)
+        s, d, i = _path_counts(path)
+        out.append(Alignment(h, r, path, ErrorCounts(s, d, i, len(r), len(h))))
+    return out
+
+
+def format_alignment(a: Alignment, width: int = 100) -> str:
+    """The three-line view of an alignment: a REF and a HYP line with each pair of items in a column of
+    equal width, `***` on the side that has no item, and under them S, D or I below every error; wrapped into
+    blocks of at most `width` characters a line (a single wider column is not cut)."""
+    cols = []
+    for op, h, r, _, _ in a.pairs():
+        show = lambda x: "***" if x is None else (str(x) if str(x).strip() else "_" * len(str(x)))  # noqa: E731
+        rs, hs = show(r), show(h)
+        w = max(len(rs), len(hs))
+        cols.append((rs.ljust(w), hs.ljust(w), " SDI"[op].ljust(w)))
+    blocks, cur, used = [], [], 5
+    for c in cols:
+        if cur and used + len(c[0]) + 1 > width:
+            blocks.append(cur)
+            cur, used = [], 5
+        cur.append(c)
+        used += len(c[0]) + 1
+    blocks.append(cur)
+    lines = []
+    for b in blocks:
+        lines += [("REF: " + " ".join(c[0] for c in b)).rstrip(), ("HYP: " + " ".join(c[1] for c in b)).rstrip(),
+                  ("     " + " ".join(c[2] for c in b)).rstrip()]
+    return "\n".join(lines)
+
+
+def confusions(alignments: Sequence[Alignment]):
+    """(substitutions, deletions, insertions) of a set of alignments as three Counters: of (ref item, hyp item)
+    pairs, of deleted reference items and of inserted hypothesis items."""
+    from collections import Counter
+    sub, dele, ins = Counter(), Counter(), Counter()
+    for a in alignments:
+        for op, h, r, _, _ in a.pairs():
+            if op == SUBSTITUTION:
+                sub[(r, h)] += 1
+            elif op == DELETION:
+                dele[r] += 1
+            elif op == INSERTION:
+                ins[h] += 1
+    return sub, dele, ins
