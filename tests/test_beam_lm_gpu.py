@@ -174,6 +174,27 @@ def test_lm_with_ragged_batch(ops, W, weight):
     record_metric("beam_lm", case=f"lm-ragged-w{W}-x{weight}", max_dscore=worst)
 
 
+def test_lm_commit_with_every_beam_live(ops):
+    """W = 32 over V = 6, L = 30, a trained table at weight 0.3, B = 5 with counts [L, 1, 0, L - 1, 7]:
+    the live set fills all 32 lanes within three frames and most winners of a frame are new nodes, so
+    S(child) and the node numbers come from the lane-per-beam commit in nearly every lane.  The batch
+    bitwise each utterance alone, and both the restatement."""
+    V, L, W, blank, weight = 6, 30, 32, 0, 0.3
+    lg, frames = C.ragged_case(V, L, blank, seed=V)
+    table = C.trained_table(np.random.default_rng(61), V, blank).table
+    x, t = torch.from_numpy(lg).to(DEV), torch.from_numpy(table).to(DEV)
+    batch = ops.ctc_beam_search(x, W, blank, frames=frames, lm_table=t, lm_weight=weight)
+    got = device_beams(*batch)
+    assert len(got[0]) == W and len(got[3]) == W
+    for b, n in enumerate(frames):
+        c = dict(name=f"lm-commit-u{b}", logits=lg[b:b + 1], lengths=[n], W=W, blank=blank, table=table, lm_weight=weight)
+        want, decided = C.expected(c)
+        alone = ops.ctc_beam_search(x[b:b + 1], W, blank, frames=[n], lm_table=t, lm_weight=weight)
+        same_bits([y[b:b + 1] for y in batch], alone, f"utterance {b} alone")
+        compare(device_beams(*alone), want, decided, c["name"])
+        compare(got[b:b + 1], want, decided, c["name"])
+
+
 # ----------------------------------------------------------------------------- public interface
 def test_public_search_runs_a_bigram_on_the_device(ops, monkeypatch):
     from velocity_asr import decode

@@ -193,6 +193,42 @@ def test_complete_mode_is_the_dense_entry(ops, c):
     same_bits(got[:4], dense(ops, c), c["name"])
 
 
+@pytest.mark.parametrize("V,L,W,blank", [(40, 12, 32, 7), (257, 9, 5, 256)])
+def test_complete_mode_on_a_ragged_batch(ops, V, L, W, blank):
+    """B = 3, counts [L, 0, L - 1], NaN past the counts: the dense kernel reading rows is bitwise the
+    dense kernel reading logits, for a device count tensor and for a host list, and certifies all."""
+    lg, _ = F.ragged_case(V, L, blank, seed=V + 2, B=3)
+    frames = [L, 0, L - 1]
+    x = torch.full((3, L, V), float("nan"), device=DEV)
+    for b, n in enumerate(frames):
+        x[b, :n] = torch.from_numpy(lg[b, :n]).to(DEV)
+    for fr in (torch.tensor(frames, dtype=torch.int32, device=DEV), frames):
+        got = ops.ctc_beam_search_shortlist(None, ops.ctc_beam_shortlist(x, 0, blank, fr), None, V, W, blank, fr)
+        assert got[4].cpu().tolist() == [0, 0, 0]
+        same_bits(got[:4], ops.ctc_beam_search(x, W, blank, frames=fr), f"{type(fr).__name__} counts")
+    assert device_beams(*got[:4])[1] == [([], 0.0)]
+
+
+def test_dense_kernel_at_its_lds_limit(ops, monkeypatch):
+    """V = 16384 is the largest row the dense kernel holds (64 KiB of dynamic LDS beside its static
+    state): bitwise the complete mode on the same logits.  V = 16385 is refused there, and the exact
+    search goes through the complete mode."""
+    from velocity_asr import decode
+    L, W, blank = 3, 2, 0
+    assert ops.BEAM_DENSE_MAX_VOCAB == 16384
+    lg = (np.random.default_rng(16384).standard_normal((1, L, 16385)) * 3.0).astype(np.float32)
+    x = torch.from_numpy(lg).to(DEV)
+    at = x[..., :16384]  # strided rows
+    full = ops.ctc_beam_search_shortlist(None, ops.ctc_beam_shortlist(at, 0, blank), None, 16384, W, blank)
+    assert full[4].cpu().tolist() == [0]
+    same_bits(ops.ctc_beam_search(at, W, blank), full[:4], "V = 16384")
+    with pytest.raises(RuntimeError, match="bad shape"):
+        ops.ctc_beam_search(x, W, blank)
+    over = ops.ctc_beam_search_shortlist(None, ops.ctc_beam_shortlist(x, 0, blank), None, 16385, W, blank)
+    monkeypatch.setattr(ops, "ctc_beam_search", lambda *a, **k: pytest.fail("the dense entry above its limit"))
+    same_bits(decode._beam_search_exact(x, W, blank, None), over[:4], "V = 16385")
+
+
 def test_large_vocabulary(ops, monkeypatch):
     """V = 20 000 (the dense entry refuses it), L = 6, W = 4: the complete mode against the
     restatement of the reference, the shortlisted search bitwise the complete mode, and the public

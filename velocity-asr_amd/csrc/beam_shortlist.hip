@@ -1,29 +1,25 @@
 // Exact CTC prefix beam search from a per-frame shortlist.
 //
 // vasr_ctc_beam_shortlist_f32: one workgroup per (utterance, frame) row forms the row's log-softmax
-// exactly as ctc_beam_kernel (beam.hip) does -- the same 256 strided partial sums through the same
-// block_reduce_f, so the same bits -- and keeps the K best non-blank tokens, ordered by
-// (log-probability descending, token ascending), with the blank's log-probability.  The selection
-// is K block-wide maxima of an order-preserving 64-bit key (float bits, ~token); each thread keeps
-// the best key of its own strided slice and only the winner's owner rescans its slice.  K = 0
-// (complete mode) writes the whole log-probability rows instead.  Up to V = 16384 the row is staged
-// in LDS, as in beam.hip; above that every pass re-reads it from global memory (L2).
+// with beam_common.h's row_log_softmax, the dense search's own, and keeps the K best non-blank tokens,
+// ordered by (log-probability descending, token ascending), with the blank's log-probability.  The
+// selection is K block-wide maxima of an order-preserving 64-bit key (float bits, ~token); each
+// thread keeps the best key of its own strided slice and only the winner's owner rescans its slice.
+// K = 0 (complete mode) writes the whole log-probability rows instead.  Up to V = 16384 the row is
+// staged in LDS, as in beam.hip; above that every pass re-reads it from global memory (L2).
 //
-// vasr_ctc_beam_search_shortlist: ctc_beam_kernel<false>'s frame step over nb * (K + 1) candidates
-// -- every live key, and every live beam extended by the frame's K tokens -- instead of nb * V.
-// One wave per utterance: the candidates of a frame (at most 32 * 65) are scored once into LDS and
-// the W winners are W wave-wide maxima over them.  Step 2 is beam.hip's and step 4 forms the same beam set
-// with lane r building beam r (new trie nodes numbered in winner order by a ballot); a live beam's
-// repeat or parent extension whose token is not in the frame's shortlist offers no score, but the
-// parent extension still offers its insertion position, which the full search would have used
-// (the key's position is structural: min(j (V + 1), src (V + 1) + ptok_j + 1)).  After the W winners
-// are known the frame is certified when the W-th winner's score is strictly above
-// fl(s_i + theta) for every live beam i, theta the shortlist's smallest log-probability: no omitted
-// candidate can then enter, raise a survivor or win its last label.  Uncertified frames are
-// counted per utterance; the search goes on either way and the caller decides.  The `complete`
-// instance (tok == NULL) reads (B, L, V) log-probability rows by token index, evaluates no
-// certificate and walks nb * V candidates with 256 threads, as beam.hip does: the exact search for
-// vocabularies whose row does not fit beam.hip's LDS.
+// vasr_ctc_beam_search_shortlist: beam_common.h's frame step over nb * (K + 1) candidates -- every live
+// key, and every live beam extended by the frame's K tokens -- instead of nb * V.  One wave per
+// utterance.  What is this file's: the frame source (the shortlist of the frame in LDS, loaded a frame
+// ahead; a token outside it is not found), the candidate cache (the candidates of a frame, at most
+// 32 * 65, are scored once into LDS, the slot of an extension that reaches an existing node struck
+// out by the live beam that owns the node, and the W winners are W wave-wide maxima over them), and the
+// certificate.  After the W winners are known the frame is certified when the W-th winner's score is
+// strictly above fl(s_i + theta) for every live beam i, theta the shortlist's smallest
+// log-probability: no omitted candidate can then enter, raise a survivor or win its last label.
+// Uncertified frames are counted per utterance; the search goes on either way and the caller decides.
+// tok == NULL (complete mode) is not searched here: it is beam.hip's dense kernel reading the (B, L, V)
+// log-probability rows by token index, the exact search for vocabularies whose row does not fit LDS.
 #include "beam_common.h"
 
 namespace vasr {
@@ -65,8 +61,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_shortlist_kernel(const floa
     const int tid = threadIdx.x;
     const int b = blockIdx.x / L, t = blockIdx.x - b * L;
     const int64_t r = blockIdx.x;
-    const int nf = frames ? min(max(frames[b], 0), L) : L;
-    if (t >= nf) {  // a row past the utterance: never read; the shortlist gets a defined fill
+    if (t >= beam_frames(frames, b, L)) {  // a row past the utterance: never read; the shortlist gets a defined fill
         if (K > 0) {
             for (int k = tid; k < K; k += kBeamThreads) {
                 out_tok[r * K + k] = -1;
@@ -77,23 +72,10 @@ __global__ __launch_bounds__(kBeamThreads) void beam_shortlist_kernel(const floa
         return;
     }
     const float* row = logits + (int64_t)b * ld_utt + (int64_t)t * ld_row;
-    // log_softmax of the row: beam.hip's step 1, operation for operation
-    float mx = -INFINITY;
-    for (int v = tid; v < V; v += kBeamThreads) {
-        const float x = row[v];
-        if (STAGED) lp[v] = x;
-        mx = fmaxf(mx, x);
-    }
-    mx = block_reduce_f(mx, fred, true);
-    float se = 0.f;
-    for (int v = tid; v < V; v += kBeamThreads) se += expf((STAGED ? lp[v] : row[v]) - mx);
-    se = block_reduce_f(se, fred, false);
-    const float lse = logf(se);
+    float mx, lse;
+    row_log_softmax<STAGED>(row, V, lp, fred, mx, lse);
+    if (STAGED) __syncthreads();
     auto value = [&](int v) { return STAGED ? lp[v] : (row[v] - mx) - lse; };
-    if (STAGED) {
-        for (int v = tid; v < V; v += kBeamThreads) lp[v] = (lp[v] - mx) - lse;
-        __syncthreads();
-    }
     if (K == 0) {  // complete mode: the whole row
         float* o = out_lp + r * V;
         for (int v = tid; v < V; v += kBeamThreads) o[v] = value(v);
@@ -130,65 +112,51 @@ __global__ __launch_bounds__(kBeamThreads) void beam_shortlist_kernel(const floa
     if (tid == 0) out_blank_lp[r] = value(blank);
 }
 
-template <int THREADS>
-__device__ __forceinline__ Cand group_best(Cand c, Cand* red) {
-    if (THREADS == kBeamThreads) return block_best(c, red);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {  // one wave: after the butterfly every lane holds the best
-        Cand d;
-        d.s = __shfl_xor(c.s, o, 64);
-        d.idx = __shfl_xor(c.idx, o, 64);
-        if (better(d, c)) c = d;
+// The frame's shortlist in LDS: a token is found by its place in it, or not at all.
+struct ShortlistSource {
+    const int* tok;
+    const float* lp;
+    const float* blank;
+    int K;
+    __device__ float blank_lp() const { return *blank; }
+    __device__ int lookup(int t, float& v) const {
+        int at = -1;
+        for (int k = 0; k < K; ++k)
+            if (tok[k] == t) {
+                v = lp[k];
+                at = k;
+            }
+        return at;
     }
-    return c;
-}
+};
 
-template <bool COMPLETE, int THREADS>
-__global__ __launch_bounds__(THREADS) void beam_shortlist_search_kernel(
+__global__ __launch_bounds__(64) void beam_shortlist_search_kernel(
     const int32_t* __restrict__ tokT, const float* __restrict__ lpT, const float* __restrict__ blankT, int L, int K, int V,
     int W, int blank, const int32_t* __restrict__ frames, int32_t* __restrict__ trie, int64_t trie_stride,
     int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len, double* __restrict__ out_score,
     int32_t* __restrict__ out_nbeams, int32_t* __restrict__ out_uncertified) {
-    static_assert(COMPLETE ? THREADS == kBeamThreads : THREADS == 64, "one wave walks a shortlist");
-    constexpr int kSlots = COMPLETE ? 1 : kMaxBeam * (kMaxShortlist + 1);
+    constexpr int kSlots = kMaxBeam * (kMaxShortlist + 1);
     __shared__ double cs[kSlots];  // the frame's candidates, scored once
     __shared__ long long ci[kSlots];
-    __shared__ int stok[COMPLETE ? 1 : kMaxShortlist];
-    __shared__ float slp[COMPLETE ? 1 : kMaxShortlist];
+    __shared__ int stok[kMaxShortlist];
+    __shared__ float slp[kMaxShortlist];
     __shared__ float sblank;
-    __shared__ double sc[kMaxBeam], msc[kMaxBeam];
-    __shared__ long long midx[kMaxBeam];
-    __shared__ int last[kMaxBeam], node[kMaxBeam], pnode[kMaxBeam], ptok[kMaxBeam], mlast[kMaxBeam];
-    __shared__ int src_of[kMaxBeam];  // beam i whose extension reaches beam j's node, or -1
-    __shared__ Cand red[kBeamThreads / 64];
-    __shared__ int slot_of[COMPLETE ? 1 : kMaxBeam];  // the shortlist slot merged into live key j, or -1
-    __shared__ int nb_s, nodes_s;
+    __shared__ BeamState<false> st;
 
     const int b = blockIdx.x, tid = threadIdx.x;
     int32_t* par = trie + (int64_t)b * trie_stride;  // parent node
     int32_t* tk = par + trie_stride / 2;             // appended token
     const long long VP = (long long)V + 1;
-    const int K1 = COMPLETE ? V : K + 1;  // candidates per live beam
-    if (tid == 0) {
-        sc[0] = 0.0;
-        last[0] = -1;  // None
-        node[0] = 0;
-        pnode[0] = -1;
-        ptok[0] = -1;
-        par[0] = -1;
-        tk[0] = -1;
-        nb_s = 1;
-        nodes_s = 1;
-    }
-    __syncthreads();
-    const int nf = frames ? min(max(frames[b], 0), L) : L;
-    int uncertified = 0;  // thread 0's count
+    const int K1 = K + 1;  // candidates per live beam
+    beam_init(st, par, tk);
+    const int nf = beam_frames(frames, b, L);
+    int uncertified = 0;
 
     // the next frame's shortlist is loaded a frame ahead
     const int64_t r0 = (int64_t)b * L;
     int ntok = -1;
     float nlp = 0.f, nbl = 0.f;
-    if (!COMPLETE && nf > 0) {
+    if (nf > 0) {
         if (tid < K) {
             ntok = tokT[r0 * K + tid];
             nlp = lpT[r0 * K + tid];
@@ -197,207 +165,50 @@ __global__ __launch_bounds__(THREADS) void beam_shortlist_search_kernel(
     }
 
     for (int t = 0; t < nf; ++t) {
-        const float* row = COMPLETE ? lpT + (r0 + t) * V : nullptr;
-        if (!COMPLETE) {
+        if (tid < K) {
+            stok[tid] = ntok;
+            slp[tid] = nlp;
+        }
+        if (tid == 0) sblank = nbl;
+        if (t + 1 < nf) {
             if (tid < K) {
-                stok[tid] = ntok;
-                slp[tid] = nlp;
+                ntok = tokT[(r0 + t + 1) * K + tid];
+                nlp = lpT[(r0 + t + 1) * K + tid];
             }
-            if (tid == 0) sblank = nbl;
-            if (t + 1 < nf) {
-                if (tid < K) {
-                    ntok = tokT[(r0 + t + 1) * K + tid];
-                    nlp = lpT[(r0 + t + 1) * K + tid];
-                }
-                if (tid == 0) nbl = blankT[r0 + t + 1];
-            }
+            if (tid == 0) nbl = blankT[r0 + t + 1];
         }
-        const int nb = nb_s;
-        // 2. merged record of every live key
-        if (tid < nb) {
-            const int j = tid;
-            int src = -1;
-            for (int i = 0; i < nb; ++i)
-                if (node[i] == pnode[j] && ptok[j] != last[i]) src = i;
-            src_of[j] = src;
-        }
-        __syncthreads();
-        if (tid < nb) {
-            const int j = tid;
-            // candidates in insertion order: (src, ptok) if src < j, (j, blank), (j, last), (src, ptok) if src > j
-            Cand best{0.0, -1};
-            int bl = -1;
-            long long first = -1;
-            auto place = [&](long long idx) {
-                if (first < 0 || idx < first) first = idx;
-            };
-            auto offer = [&](double s, long long idx, int lt) {
-                place(idx);
-                if (best.idx < 0 || s > best.s || (s == best.s && idx < best.idx)) {
-                    best.s = s;
-                    best.idx = idx;
-                    bl = lt;
-                }
-            };
-            // the frame's log-probability of a token: by index, or by its place in the shortlist
-            auto lookup = [&](int tok, float& v) {  // its place in the shortlist (any value >= 0 by index), or -1
-                if (COMPLETE) {
-                    v = row[tok];
-                    return 0;
-                }
-                int at = -1;
-                for (int k = 0; k < K; ++k)
-                    if (stok[k] == tok) {
-                        v = slp[k];
-                        at = k;
-                    }
-                return at;
-            };
-            const int src = src_of[j];
-            float v = 0.f;
-            int merged = -1;  // the candidate slot of (src, ptok): an existing node, merged into key j
-            offer(sc[j] + (double)(COMPLETE ? row[blank] : sblank), (long long)j * VP, blank);
-            if (last[j] >= 0 && last[j] != blank && lookup(last[j], v) >= 0)
-                offer(sc[j] + (double)v, (long long)j * VP + last[j] + 1, last[j]);
-            if (src >= 0) {
-                const long long idx = (long long)src * VP + ptok[j] + 1;
-                const int at = lookup(ptok[j], v);
-                if (at >= 0) {
-                    offer(sc[src] + (double)v, idx, ptok[j]);
-                    merged = src * K1 + at + 1;
-                } else {
-                    place(idx);  // the full search inserts the key here, whatever the score
-                }
-            }
-            if (!COMPLETE) slot_of[j] = merged;
-            msc[j] = best.s;
-            midx[j] = first;
-            mlast[j] = bl;
-        }
-        __syncthreads();
-        // 3. W best candidates, each the maximum strictly below the previous winner
+        const int nb = st.nb;
+        beam_merge(st, ShortlistSource{stok, slp, &sblank, K}, nb, V, blank, 0.0);
+        // the candidates: slot i * K1 is live key i, slot i * K1 + k + 1 beam i extended by the k-th token
         const int ncand = nb * K1;
-        auto candidate = [&](int c) {
+        for (int c = tid; c < ncand; c += 64) {
             const int i = c / K1, k = c - i * K1;
             Cand cd{0.0, -1};
-            if (COMPLETE ? k == blank : k == 0) {
-                cd.s = msc[i];
-                cd.idx = midx[i];
-                return cd;
+            if (k == 0) {
+                cd.s = st.msc[i];
+                cd.idx = st.midx[i];
+            } else if (stok[k - 1] != st.last[i]) {
+                cd.s = st.sc[i] + (double)slp[k - 1];
+                cd.idx = (long long)i * VP + stok[k - 1] + 1;
             }
-            const int tok = COMPLETE ? k : stok[k - 1];
-            if (tok == last[i]) return cd;
-            if (COMPLETE)  // (the shortlist's slots of existing nodes are struck out below, by slot_of)
-                for (int j = 0; j < nb; ++j)
-                    if (src_of[j] == i && ptok[j] == tok) return cd;  // an existing node: merged into key j
-            cd.s = sc[i] + (double)(COMPLETE ? row[tok] : slp[k - 1]);
-            cd.idx = (long long)i * VP + tok + 1;
-            return cd;
-        };
-        if (!COMPLETE) {
-            for (int c = tid; c < ncand; c += THREADS) {
-                const Cand cd = candidate(c);
-                cs[c] = cd.s;
-                ci[c] = cd.idx;
-            }
-            __syncthreads();
-            if (tid < nb && slot_of[tid] >= 0) ci[slot_of[tid]] = -1;
-            __syncthreads();
-        }
-        Cand prev{INFINITY, -2}, mywin{0.0, -1};  // lane r keeps winner r
-        int nw = 0;
-        for (int r = 0; r < W; ++r) {
-            Cand mine{0.0, -1};
-            for (int c = tid; c < ncand; c += THREADS) {
-                Cand k;
-                if (COMPLETE) {
-                    k = candidate(c);
-                } else {  // this thread's own slots: no barrier needed
-                    k.s = cs[c];
-                    k.idx = ci[c];
-                }
-                if (k.idx < 0) continue;
-                // below the previous winner in the sorted order
-                if (prev.idx != -2 && !(prev.s > k.s || (prev.s == k.s && prev.idx < k.idx))) continue;
-                if (better(k, mine)) mine = k;
-            }
-            const Cand w = group_best<THREADS>(mine, red);
-            if (w.idx < 0) break;
-            if (tid == r) mywin = w;
-            prev = w;
-            ++nw;
-        }
-        // 4. the new beam set in winner order, lane r forming beam r, and the certificate
-        double rsc = 0.0;
-        int rlast = -1, rnode = 0, rpn = -1, rpt = -1;
-        bool fresh = false;  // a new trie node
-        if (tid < nw) {
-            const long long idx = mywin.idx;
-            const int i = (int)(idx / VP);
-            const int pos = (int)(idx - (long long)i * VP);  // 0 = blank, tok + 1 otherwise
-            int key_beam = -1;
-            for (int j = 0; j < nb; ++j)
-                if (midx[j] == idx) key_beam = j;
-            if (key_beam >= 0) {
-                const int j = key_beam;
-                rsc = msc[j];
-                rlast = mlast[j];
-                rnode = node[j];
-                rpn = pnode[j];
-                rpt = ptok[j];
-            } else {
-                fresh = true;
-                rsc = mywin.s;
-                rlast = rpt = pos - 1;
-                rpn = node[i];
-            }
-        }
-        // new nodes are numbered in winner order (lanes r < nw <= 32 are all in the first wave)
-        const unsigned long long fm = __ballot(fresh);
-        const int base = nodes_s;
-        if (fresh) rnode = base + __popcll(fm & ((1ull << tid) - 1));
-        bool bad = false;
-        if (!COMPLETE && K < V - 1) {
-            bad = nw != W;
-            if (!bad) {  // prev is the W-th winner
-                const double sigma = prev.s, theta = (double)slp[K - 1];
-                bad = __ballot(tid < nb && !(sigma > sc[tid] + theta)) != 0;  // a NaN fails
-            }
-        }
-        __syncthreads();  // every lane has read the old beams
-        if (tid < nw) {
-            sc[tid] = rsc;
-            last[tid] = rlast;
-            node[tid] = rnode;
-            pnode[tid] = rpn;
-            ptok[tid] = rpt;
-            if (fresh) {
-                par[rnode] = rpn;
-                tk[rnode] = rpt;
-            }
-        }
-        if (tid == 0) {
-            nb_s = nw;
-            nodes_s = base + __popcll(fm);
-            if (bad) ++uncertified;
+            cs[c] = cd.s;
+            ci[c] = cd.idx;
         }
         __syncthreads();
+        if (tid < nb && st.slot_of[tid] >= 0) ci[st.src_of[tid] * K1 + st.slot_of[tid] + 1] = -1;  // merged into key tid
+        __syncthreads();
+        Cand mywin, sigma;  // sigma: the W-th winner where nw == W
+        const int nw = beam_select<64>(ncand, W, [&](int c) { return Cand{cs[c], ci[c]}; }, nullptr, mywin, sigma);
+        // the certificate, from the old scores
+        if (K < V - 1) {
+            bool bad = nw != W;
+            if (!bad) bad = __ballot(tid < nb && !(sigma.s > st.sc[tid] + (double)slp[K - 1])) != 0;  // a NaN fails
+            if (bad) ++uncertified;
+        }
+        beam_commit(st, nb, nw, mywin, V, par, tk, BeamLM{});
     }
-    // results: beams are already in the reference's final sorted order
-    const int nb = nb_s;
-    if (tid < nb) {
-        int len = 0;
-        for (int n = node[tid]; n > 0; n = par[n]) ++len;
-        int32_t* o = out_tokens + ((int64_t)b * W + tid) * L;
-        int k = len;
-        for (int n = node[tid]; n > 0; n = par[n]) o[--k] = tk[n];
-        out_len[(int64_t)b * W + tid] = len;
-        out_score[(int64_t)b * W + tid] = sc[tid];
-    }
-    if (tid == 0) {
-        out_nbeams[b] = nb;
-        out_uncertified[b] = uncertified;
-    }
+    beam_write(st, par, tk, b, L, W, out_tokens, out_len, out_score, out_nbeams);
+    if (tid == 0) out_uncertified[b] = uncertified;
 }
 
 }  // namespace
@@ -418,7 +229,7 @@ VASR_API int vasr_ctc_beam_shortlist_f32(const float* logits, int64_t ld_row, in
                    who);
     if ((int64_t)B * L == 0) return VASR_OK;
     if (K > V - 1) K = V - 1;
-    const bool staged = V <= 16384;  // beam.hip's limit: the row in 64 KiB of LDS
+    const bool staged = V <= kMaxStagedVocab;
     hipLaunchKernelGGL(staged ? beam_shortlist_kernel<true> : beam_shortlist_kernel<false>, dim3(B * L), dim3(kBeamThreads),
                        staged ? V * sizeof(float) : 0, as_stream(stream), logits, ld_row, ld_utt, L, V, K, blank, frames,
                        out_tok, out_lp, out_blank_lp);
@@ -431,23 +242,21 @@ VASR_API int vasr_ctc_beam_search_shortlist(const int32_t* tok, const float* lp,
                                             int32_t* out_uncertified, void* stream) {
     using namespace vasr;
     const char* who = "vasr_ctc_beam_search_shortlist";
-    VASR_CHECK_ARG(trie && out_tokens && out_len && out_score && out_nbeams && out_uncertified, "%s: null pointer", who);
-    VASR_CHECK_ARG(B >= 0 && L >= 0 && V >= 1 && V <= (1 << 20) && W >= 1 && W <= kMaxBeam && blank >= 0 && blank < V,
-                   "%s: bad shape B=%d L=%d V=%d W=%d blank=%d", who, B, L, V, W, blank);
+    if (int rc = beam_check_args(who, trie && out_tokens && out_len && out_score && out_nbeams && out_uncertified, B, L, V,
+                                 1 << 20, W, blank))
+        return rc;
     const bool complete = tok == nullptr;
     VASR_CHECK_ARG(lp || (int64_t)B * L == 0, "%s: null pointer", who);
     VASR_CHECK_ARG(complete || (blank_lp || (int64_t)B * L == 0), "%s: a shortlist without its blank column", who);
     VASR_CHECK_ARG(complete || (K >= 1 && K <= kMaxShortlist && K <= V - 1), "%s: K=%d outside 1..min(%d, V - 1) for V=%d",
                    who, K, kMaxShortlist, V);
     if (B == 0) return VASR_OK;
-    const int64_t stride = vasr_ctc_beam_workspace_elems(L, W);
-    if (complete)
-        hipLaunchKernelGGL((beam_shortlist_search_kernel<true, kBeamThreads>), dim3(B), dim3(kBeamThreads), 0,
-                           as_stream(stream), tok, lp, blank_lp, L, K, V, W, blank, frames, trie, stride, out_tokens, out_len,
-                           out_score, out_nbeams, out_uncertified);
+    if (complete)  // the dense kernel over the rows
+        beam_launch(lp, V, (int64_t)L * V, B, L, V, W, blank, frames, nullptr, 0, 0.0, trie, out_tokens, out_len, out_score,
+                    out_nbeams, out_uncertified, stream);
     else
-        hipLaunchKernelGGL((beam_shortlist_search_kernel<false, 64>), dim3(B), dim3(64), 0, as_stream(stream), tok, lp,
-                           blank_lp, L, K, V, W, blank, frames, trie, stride, out_tokens, out_len, out_score, out_nbeams,
+        hipLaunchKernelGGL(beam_shortlist_search_kernel, dim3(B), dim3(64), 0, as_stream(stream), tok, lp, blank_lp, L, K, V, W,
+                           blank, frames, trie, vasr_ctc_beam_workspace_elems(L, W), out_tokens, out_len, out_score, out_nbeams,
                            out_uncertified);
     return launch_status(who);
 }

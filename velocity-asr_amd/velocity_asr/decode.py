@@ -229,8 +229,8 @@ def beam_shortlist_size(shortlist, vocab_size: int, beam_width: int) -> int:
 
 def _beam_search_exact(logits: torch.Tensor, beam_width: int, blank: int, frames):
     """The full search (every token a candidate in every frame) of the utterances a shortlist did
-    not certify: the dense kernel where the vocabulary fits it, else complete log-probability rows
-    and the shortlist kernel's complete instance."""
+    not certify: the dense kernel on the logits where a row fits its LDS, else complete
+    log-probability rows and the same kernel reading those (the shortlist entry's complete mode)."""
     V = logits.shape[-1]
     if V <= ops.BEAM_DENSE_MAX_VOCAB:
         return ops.ctc_beam_search(logits, beam_width, blank, frames=frames)

@@ -1400,11 +1400,7 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0, *, fr
         if tuple(lm_table.shape) != (V + 1, V):
             raise ValueError(f"ctc_beam_search: lm_table must be ({V + 1}, {V}), got {tuple(lm_table.shape)}")
         tab = lm_table if lm_table.stride(-1) == 1 else lm_table.contiguous()
-    trie = torch.empty(max(B, 1) * int(L.lib().vasr_ctc_beam_workspace_elems(Lq, W)), device=dev, dtype=torch.int32)
-    toks = torch.zeros((B, W, max(Lq, 1)), device=dev, dtype=torch.int32)
-    lens = torch.zeros((B, W), device=dev, dtype=torch.int32)
-    scores = torch.zeros((B, W), device=dev, dtype=torch.float64)
-    nbeams = torch.zeros((B,), device=dev, dtype=torch.int32)
+    trie, toks, lens, scores, nbeams = _beam_buffers(B, Lq, W, dev)
     if fr is None and tab is None:
         check(L.lib().vasr_ctc_beam_search(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, W, int(blank),
                                            trie.data_ptr(), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
@@ -1419,6 +1415,17 @@ def ctc_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0, *, fr
 
 BEAM_SHORTLIST_MAX = 64  # tokens per frame of a shortlist (csrc/beam_shortlist.hip)
 BEAM_DENSE_MAX_VOCAB = 16384  # vasr_ctc_beam_search[_lm]: the row's log-probabilities live in LDS
+
+
+def _beam_buffers(B: int, Lq: int, W: int, dev):
+    """The trie workspace of a beam search entry and its four outputs (tokens, lengths, scores, beams
+    per utterance), zeroed."""
+    trie = torch.empty(max(B, 1) * int(L.lib().vasr_ctc_beam_workspace_elems(Lq, W)), device=dev, dtype=torch.int32)
+    toks = torch.zeros((B, W, max(Lq, 1)), device=dev, dtype=torch.int32)
+    lens = torch.zeros((B, W), device=dev, dtype=torch.int32)
+    scores = torch.zeros((B, W), device=dev, dtype=torch.float64)
+    nbeams = torch.zeros((B,), device=dev, dtype=torch.int32)
+    return trie, toks, lens, scores, nbeams
 
 
 def _beam_frames(who: str, frames, B: int, Lq: int, device) -> Optional[torch.Tensor]:
@@ -1501,11 +1508,7 @@ def ctc_beam_search_shortlist(tok: Optional[torch.Tensor], lp: torch.Tensor, bla
         if not 1 <= K <= min(BEAM_SHORTLIST_MAX, V - 1):
             raise ValueError(f"ctc_beam_search_shortlist: K = {K} outside 1..{min(BEAM_SHORTLIST_MAX, V - 1)} for V = {V}")
     fr = _beam_frames("ctc_beam_search_shortlist", frames, B, Lq, dev)
-    trie = torch.empty(max(B, 1) * int(L.lib().vasr_ctc_beam_workspace_elems(Lq, W)), device=dev, dtype=torch.int32)
-    toks = torch.zeros((B, W, max(Lq, 1)), device=dev, dtype=torch.int32)
-    lens = torch.zeros((B, W), device=dev, dtype=torch.int32)
-    scores = torch.zeros((B, W), device=dev, dtype=torch.float64)
-    nbeams = torch.zeros((B,), device=dev, dtype=torch.int32)
+    trie, toks, lens, scores, nbeams = _beam_buffers(B, Lq, W, dev)
     unc = torch.zeros((B,), device=dev, dtype=torch.int32)
     check(L.lib().vasr_ctc_beam_search_shortlist(ptr(tok), lp.data_ptr(), ptr(blank_lp), B, Lq, 0 if tok is None else K, V,
                                                  W, int(blank), ptr(fr), trie.data_ptr(), toks.data_ptr(), lens.data_ptr(),
