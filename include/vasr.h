@@ -750,6 +750,40 @@ int vasr_ctc_beam_search_shortlist(const int32_t* tok, const float* lp, const fl
                                    int32_t* out_tokens, int32_t* out_len, double* out_score,
                                    int32_t* out_nbeams, int32_t* out_uncertified, void* stream);
 
+/* The standard CTC prefix beam search (not the reference's, which the entries above
+ * restate): a prefix carries the summed log-probability of all its alignments, pb over those ending
+ * in the blank and pnb over those ending in its tail token (float64, joined by logaddexp, start
+ * pb = 0, pnb = -inf for the empty prefix).  Per frame, live beam i (tot = pb (+) pnb) gives
+ * tot + lp[blank] to its own pb, pnb + lp[tail] to its own pnb, pb + lp[tail] to prefix + (tail) and
+ * tot + lp[tok] to prefix + (tok) for every other non-blank token; contributions to one prefix are
+ * summed, a contribution of -inf is not made.  The W prefixes of largest
+ *   rank = ((pb (+) pnb) + alpha * S(prefix)) + beta * len(prefix)
+ * survive (ties: the reference's insertion order, position i (V + 1) + tok + 1, the blank's at
+ * i (V + 1), and at the position of a repeated tail the prefix's own key before the extension); S is the bigram table's left-to-right float64 sum, so a token's language-model score is
+ * added once, when it is appended, and beta is a per-token length bonus.
+ * logits, ld_row, ld_utt, B, L, V <= 16384, W <= 32, blank, frames, lm_table, ld_lm, trie, out_tokens,
+ * out_len and out_nbeams as vasr_ctc_beam_search_lm; the table is active when lm_table != NULL and
+ * alpha > 0; alpha and beta must not be NaN.  out_score[b*W + r] = rank, out_logp[b*W + r] =
+ * pb (+) pnb, the log-probability of the prefix given the frames (under the beam's pruning).  A frame
+ * count of 0 gives the single empty beam with out_logp = out_score = 0.0. */
+int vasr_ctc_prefix_beam_search(const float* logits, int64_t ld_row, int64_t ld_utt, int B, int L, int V,
+                                int W, int blank, const int32_t* frames, const float* lm_table,
+                                int64_t ld_lm, double alpha, double beta, int32_t* trie, int32_t* out_tokens,
+                                int32_t* out_len, double* out_score, double* out_logp, int32_t* out_nbeams,
+                                void* stream);
+
+/* The same search with token pruning: the frame's candidates are the blank and the K tokens of
+ * vasr_ctc_beam_shortlist_f32's arrays (tok, lp (B, L, K), blank_lp (B, L), 1 <= K <= min(64, V - 1));
+ * every other token counts as -inf, while the log-probabilities stay those of the full softmax.  An
+ * approximation: no certificate, no fallback.  V (up to 2^20) is the vocabulary the tokens come from;
+ * an entry that is the blank or outside 0 .. V - 1 is skipped.  Everything else as above. */
+int vasr_ctc_prefix_beam_search_shortlist(const int32_t* tok, const float* lp, const float* blank_lp, int K,
+                                          int V, int B, int L, int W, int blank, const int32_t* frames,
+                                          const float* lm_table, int64_t ld_lm, double alpha, double beta,
+                                          int32_t* trie, int32_t* out_tokens, int32_t* out_len,
+                                          double* out_score, double* out_logp, int32_t* out_nbeams,
+                                          void* stream);
+
 /* Greedy CTC collapse per utterance (decode.py:51-69, :89-123): drop blank (and reset
  * prev), skip repeats of prev if collapse != 0.  out_tokens (B, L) holds each
  * utterance's kept tokens left-aligned, out_len (B) their counts.  If out_start /

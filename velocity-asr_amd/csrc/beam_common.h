@@ -5,7 +5,9 @@
 // blank's log-probability and lookup(tok, v) -- and its candidates; everything exact lives here: the
 // beam state, the merged records with their tie rules (beam_merge), the W maxima (beam_select), the
 // new beam set and trie nodes (beam_commit), the write-out, and the row log-softmax that the dense
-// kernel and the shortlist kernel share.
+// kernel and the shortlist kernel share.  The second half of the file is the frame step of the standard
+// prefix beam search (beam_prefix.hip: summed alignments, per-token LM term, length bonus) on the same
+// trie, frame sources, selection and output layout.
 //
 // One workgroup per utterance walks the frames.  The reference keys its beams by the collapsed prefix
 // tuple; here each prefix is a node of a per-utterance trie (parent node, appended token) held in
@@ -151,6 +153,27 @@ struct RowSource {
     __device__ int lookup(int tok, float& v) const {  // always found
         v = lp[tok];
         return 0;
+    }
+};
+
+constexpr int kMaxShortlist = 64;
+
+// A frame's shortlist in LDS (vasr_ctc_beam_shortlist_f32's arrays): a token is found by its place
+// in it, or not at all.
+struct ShortlistSource {
+    const int* tok;
+    const float* lp;
+    const float* blank;
+    int K;
+    __device__ float blank_lp() const { return *blank; }
+    __device__ int lookup(int t, float& v) const {
+        int at = -1;
+        for (int k = 0; k < K; ++k)
+            if (tok[k] == t) {
+                v = lp[k];
+                at = k;
+            }
+        return at;
     }
 };
 
@@ -344,6 +367,267 @@ __device__ void beam_write(const BeamState<LM>& st, const int32_t* par, const in
         for (int n = st.node[tid]; n > 0; n = par[n]) o[--k] = tk[n];
         out_len[(int64_t)b * W + tid] = len;
         out_score[(int64_t)b * W + tid] = st.sc[tid];
+    }
+    if (tid == 0) out_nbeams[b] = nb;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The standard CTC prefix beam search (beam_prefix.hip), on the same trie, frame
+// sources, selection and output layout.  A live beam carries the summed log-probability of all
+// alignments of its prefix, split into those ending in the blank (pb) and in the prefix's tail token
+// (pnb); equal prefixes merge by logaddexp, the language model scores a token once, when it is
+// appended (alpha * table entry), and every token earns a length bonus beta.  A key's rank is
+// ((pb (+) pnb) + alpha * S(key)) + beta * len(key).
+//
+// A candidate's Cand::idx here is prefix_order(position, extension), not the bare position: at position
+// i (V + 1) + tail_i + 1 beam i both repeats its tail (into its own key) and extends by it (into
+// prefix + (tail)), the repeat first, so two keys can share a position -- they do whenever the blank is
+// -inf and the own key's first contribution is the repeat.  The order value keeps the insertion order
+// and names exactly one key: (i, slot, own) is beam i's key, (i, tok + 1, extension) is prefix_i + (tok).
+
+__device__ __forceinline__ long long prefix_order(long long position, bool extension) {
+    return 2 * position + (extension ? 1 : 0);
+}
+
+// log(exp(a) + exp(b)) in float64, x (+) -inf = x exactly.  Symmetric in its arguments.
+__device__ __forceinline__ double log_add(double a, double b) {
+    if (!(a > -INFINITY)) return b;
+    if (!(b > -INFINITY)) return a;
+    const double m = a >= b ? a : b, n = a >= b ? b : a;
+    return m + log1p(exp(n - m));
+}
+
+// (tot + alpha * S) + bonus, bonus = beta * len already rounded: products rounded before the sums,
+// as the float64 host arithmetic forms them (see add_lm).
+template <bool LM>
+__device__ __forceinline__ double prefix_rank(double tot, double alpha, double S, double bonus) {
+#pragma clang fp contract(off)
+    double s = tot;
+    if (LM) {
+        const double term = alpha * S;
+        s = s + term;
+    }
+    return s + bonus;
+}
+
+__device__ __forceinline__ double length_bonus(double beta, int len) {
+#pragma clang fp contract(off)
+    return beta * (double)len;
+}
+
+// The live beams of one utterance (LDS), in sorted order, and the merged records of their keys.
+template <bool LM>
+struct PrefixState {
+    double pb[kMaxBeam], pnb[kMaxBeam], tot[kMaxBeam], rank[kMaxBeam];
+    double lms[LM ? kMaxBeam : 1];  // S(prefix)
+    double bext[kMaxBeam];          // beta * (len + 1): the bonus of every extension of the beam
+    double mpb[kMaxBeam], mpnb[kMaxBeam], mtot[kMaxBeam], mrank[kMaxBeam];
+    long long midx[kMaxBeam];  // the key's prefix_order, -1: no finite contribution, no key
+    int len[kMaxBeam], node[kMaxBeam], pnode[kMaxBeam], ptok[kMaxBeam];  // ptok: the prefix's tail token
+    int src_of[kMaxBeam];  // the beam whose node is beam j's parent, or -1
+    int fpar[kMaxBeam], ftok[kMaxBeam], found[kMaxBeam];  // prefix_commit: a winner's (parent, token), its old node
+    int nb, nodes;
+};
+
+template <bool LM>
+__device__ void prefix_init(PrefixState<LM>& st, int32_t* par, int32_t* tk) {
+    if (threadIdx.x == 0) {
+        st.pb[0] = 0.0;
+        st.pnb[0] = -INFINITY;
+        st.tot[0] = 0.0;
+        st.rank[0] = 0.0;
+        st.lms[0] = 0.0;
+        st.len[0] = 0;
+        st.node[0] = 0;
+        st.pnode[0] = -1;
+        st.ptok[0] = -1;
+        par[0] = -1;
+        tk[0] = -1;
+        st.nb = 1;
+        st.nodes = 1;
+    }
+    __syncthreads();
+}
+
+// The merged record of every live key j.  Three contributions can reach it: its own blank extension
+// (to pb, at position j (V + 1)), its own repeat of the tail token (pnb_j + lp[tail], to pnb, at
+// j (V + 1) + tail + 1) and the extension by that token of the one beam i whose node is j's parent
+// ((tail_i == tail_j ? pb_i : tot_i) + lp[tail_j], to pnb, at i (V + 1) + tail_j + 1).  A contribution
+// of -inf -- a token the source does not hold included -- is not made: it gives no position, and a key
+// without a contribution does not exist in this frame.  The key's order is the smallest prefix_order of
+// its contributions, the parent's being an extension.  The first barrier publishes the frame source.
+template <bool LM, class Source>
+__device__ __forceinline__ void prefix_merge(PrefixState<LM>& st, const Source& f, int nb, int V, double alpha,
+                                             double beta) {
+    const int j = threadIdx.x;
+    const long long VP = (long long)V + 1;
+    int src = -1;
+    if (j < nb) {
+        for (int i = 0; i < nb; ++i)
+            if (st.node[i] == st.pnode[j]) src = i;
+        st.src_of[j] = src;
+        st.bext[j] = length_bonus(beta, st.len[j] + 1);
+    }
+    __syncthreads();
+    if (j < nb) {
+        long long first = -1;
+        auto place = [&](long long idx) {
+            if (first < 0 || idx < first) first = idx;
+        };
+        double mpb = st.tot[j] + (double)f.blank_lp(), mpnb = -INFINITY;
+        if (mpb > -INFINITY)
+            place(prefix_order((long long)j * VP, false));
+        else
+            mpb = -INFINITY;
+        const int tail = st.ptok[j];
+        float v = 0.f;
+        if (tail >= 0 && f.lookup(tail, v) >= 0) {
+            const double own = st.pnb[j] + (double)v;
+            if (own > -INFINITY) {
+                mpnb = own;
+                place(prefix_order((long long)j * VP + tail + 1, false));
+            }
+            if (src >= 0) {
+                const double ext = (st.ptok[src] == tail ? st.pb[src] : st.tot[src]) + (double)v;
+                if (ext > -INFINITY) {
+                    mpnb = log_add(mpnb, ext);
+                    place(prefix_order((long long)src * VP + tail + 1, true));
+                }
+            }
+        }
+        const double mtot = log_add(mpb, mpnb);
+        st.mpb[j] = mpb;
+        st.mpnb[j] = mpnb;
+        st.mtot[j] = mtot;
+        st.mrank[j] = prefix_rank<LM>(mtot, alpha, LM ? st.lms[j] : 0.0, length_bonus(beta, st.len[j]));
+        st.midx[j] = first;
+    }
+    __syncthreads();
+}
+
+// Beam i extended by a token of log-probability v that is not the blank: none when the extension
+// reaches a live node (it is in that key's merged record) or is -inf, else the fresh key's rank, scored
+// on the fly: after a repeat of the tail only the alignments ending in the blank go on.
+template <bool LM>
+__device__ __forceinline__ Cand prefix_fresh(const PrefixState<LM>& st, int nb, int i, int tok, float v, long long VP,
+                                             const BeamLM& lm) {
+    Cand k{0.0, -1};
+    bool existing = false;
+    for (int j = 0; j < nb; ++j)
+        if (st.src_of[j] == i && st.ptok[j] == tok) existing = true;
+    if (existing) return k;
+    const double a = (tok == st.ptok[i] ? st.pb[i] : st.tot[i]) + (double)v;
+    if (!(a > -INFINITY)) return k;
+    k.s = prefix_rank<LM>(a, lm.weight, LM ? st.lms[i] + lm.entry(st.ptok[i], tok) : 0.0, st.bext[i]);
+    k.idx = prefix_order((long long)i * VP + tok + 1, true);
+    return k;
+}
+
+// The new beam set in winner order (beam_commit's numbering of new nodes).  A surviving key takes its
+// merged record; an extension that reached no live node has pb = -inf, pnb = its one contribution,
+// S(child) = S(parent) + table[1 + tail(parent)][tok] and one more token.  Its node is the trie's own
+// (parent node, token) node where the prefix was live before, else a new one: with summed alignments a
+// prefix can leave the beam while an extension of it stays and come back later, and the extension
+// must still find it as its parent, so a prefix keeps one node for the whole search.  The old node is
+// looked for by all threads among the nodes above the smallest parent (a child is younger than its
+// parent): at most L W / 256 coalesced loads per thread and frame, each compared with the nw pairs in LDS,
+// beside nb V / 256 candidates scored W times (timed with short prefixes live late: profiles/beam_prefix.md).
+template <bool LM, class Source>
+__device__ __forceinline__ void prefix_commit(PrefixState<LM>& st, const Source& f, int nb, int nw, const Cand& mywin, int V,
+                                              int32_t* par, int32_t* tk, const BeamLM& lm) {
+    const int tid = threadIdx.x;
+    const long long VP = (long long)V + 1;
+    double rpb = -INFINITY, rpnb = -INFINITY, rtot = -INFINITY, rlms = 0.0;
+    int rlen = 0, rnode = 0, rpn = -1, rpt = -1;
+    bool fresh = false;
+    if (tid < nw) {
+        const long long idx = mywin.idx, pos = idx >> 1;  // prefix_order: one key per value
+        const int i = (int)(pos / VP);
+        int key_beam = -1;
+        for (int j = 0; j < nb; ++j)
+            if (st.midx[j] == idx) key_beam = j;
+        if (key_beam >= 0) {
+            const int j = key_beam;
+            rpb = st.mpb[j];
+            rpnb = st.mpnb[j];
+            rtot = st.mtot[j];
+            if (LM) rlms = st.lms[j];
+            rlen = st.len[j];
+            rnode = st.node[j];
+            rpn = st.pnode[j];
+            rpt = st.ptok[j];
+        } else {
+            fresh = true;
+            rpt = (int)(pos - (long long)i * VP) - 1;
+            float v = 0.f;
+            f.lookup(rpt, v);  // a winner's token is in the source
+            rpnb = rtot = (rpt == st.ptok[i] ? st.pb[i] : st.tot[i]) + (double)v;
+            rpn = st.node[i];
+            rlen = st.len[i] + 1;
+            if (LM) rlms = st.lms[i] + lm.entry(st.ptok[i], rpt);
+        }
+    }
+    const int base = st.nodes;
+    if (tid < nw) {
+        st.fpar[tid] = fresh ? rpn : -1;
+        st.ftok[tid] = rpt;
+        st.found[tid] = -1;
+    }
+    __syncthreads();
+    int lo = base;
+    for (int r = 0; r < nw; ++r)
+        if (st.fpar[r] >= 0) lo = min(lo, st.fpar[r] + 1);
+    for (int n = lo + tid; n < base; n += kBeamThreads) {
+        const int p = par[n], t = tk[n];
+        for (int r = 0; r < nw; ++r)
+            if (st.fpar[r] == p && st.ftok[r] == t) st.found[r] = n;  // at most one node per (parent, token)
+    }
+    __syncthreads();  // also: every lane has read the old beams
+    if (fresh && st.found[tid] >= 0) {
+        rnode = st.found[tid];
+        fresh = false;
+    }
+    // as beam_commit: nw <= 32, so every committing lane and thread 0 sit in wave 0
+    const unsigned long long fm = __ballot(fresh);
+    if (fresh) rnode = base + __popcll(fm & ((1ull << tid) - 1));
+    if (tid < nw) {
+        st.pb[tid] = rpb;
+        st.pnb[tid] = rpnb;
+        st.tot[tid] = rtot;
+        st.rank[tid] = mywin.s;
+        if (LM) st.lms[tid] = rlms;
+        st.len[tid] = rlen;
+        st.node[tid] = rnode;
+        st.pnode[tid] = rpn;
+        st.ptok[tid] = rpt;
+        if (fresh) {
+            // at most W nodes are created per frame, so rnode <= L W: inside the 1 + L W nodes of
+            // vasr_ctc_beam_workspace_elems, as in the reference-semantics searches
+            par[rnode] = rpn;
+            tk[rnode] = rpt;
+        }
+    }
+    if (tid == 0) {
+        st.nb = nw;
+        st.nodes = base + __popcll(fm);
+    }
+    __syncthreads();
+}
+
+template <bool LM>
+__device__ void prefix_write(const PrefixState<LM>& st, const int32_t* par, const int32_t* tk, int b, int L, int W,
+                             int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
+                             double* __restrict__ out_score, double* __restrict__ out_logp,
+                             int32_t* __restrict__ out_nbeams) {
+    const int tid = threadIdx.x, nb = st.nb;
+    if (tid < nb) {
+        const int len = st.len[tid];
+        int32_t* o = out_tokens + ((int64_t)b * W + tid) * L;
+        int k = len;
+        for (int n = st.node[tid]; n > 0 && k > 0; n = par[n]) o[--k] = tk[n];
+        out_len[(int64_t)b * W + tid] = len;
+        out_score[(int64_t)b * W + tid] = st.rank[tid];
+        out_logp[(int64_t)b * W + tid] = st.tot[tid];
     }
     if (tid == 0) out_nbeams[b] = nb;
 }

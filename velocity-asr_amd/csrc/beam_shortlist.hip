@@ -25,8 +25,6 @@
 namespace vasr {
 namespace {
 
-constexpr int kMaxShortlist = 64;
-
 __device__ __forceinline__ unsigned long long shortlist_key(float lp, int tok) {
     uint32_t u = __float_as_uint(lp + 0.0f);  // -0.0 orders as +0.0
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -111,24 +109,6 @@ __global__ __launch_bounds__(kBeamThreads) void beam_shortlist_kernel(const floa
     }
     if (tid == 0) out_blank_lp[r] = value(blank);
 }
-
-// The frame's shortlist in LDS: a token is found by its place in it, or not at all.
-struct ShortlistSource {
-    const int* tok;
-    const float* lp;
-    const float* blank;
-    int K;
-    __device__ float blank_lp() const { return *blank; }
-    __device__ int lookup(int t, float& v) const {
-        int at = -1;
-        for (int k = 0; k < K; ++k)
-            if (tok[k] == t) {
-                v = lp[k];
-                at = k;
-            }
-        return at;
-    }
-};
 
 __global__ __launch_bounds__(64) void beam_shortlist_search_kernel(
     const int32_t* __restrict__ tokT, const float* __restrict__ lpT, const float* __restrict__ blankT, int L, int K, int V,

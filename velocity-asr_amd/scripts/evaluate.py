@@ -9,6 +9,8 @@ Same command line and printed report as the reference's scripts/evaluate.py:
 --test-set takes a TSV manifest (`audio_path<TAB>reference text`); the reference's
 dataset loader is a stub that loads nothing. --beam-width > 1 selects prefix beam search, one
 launch per batch; --lm FILE.npz --lm-weight X fuses a bigram table (decode.BigramLM.save) into it.
+--search prefix runs the standard CTC prefix beam search instead of the reference's (alignments summed,
+the LM term and --length-bonus once per token, --token-topk tokens per frame).
 WER and CER are scored on --device (one batched edit-distance launch per unit); --error-breakdown adds the
 substitution / deletion / insertion totals to the report, --per-utterance FILE writes them per file.
 --alignments FILE writes each file's word alignment (which word for which), --confusions N appends the most
@@ -47,6 +49,12 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=16, help="Max equal-length files per device batch")
     p.add_argument("--lm", default=None, help="Bigram language model for beam search (.npz of BigramLM.save)")
     p.add_argument("--lm-weight", type=float, default=0.0, help="Weight of the language model score (0 = off)")
+    p.add_argument("--search", choices=("reference", "prefix"), default="reference",
+                   help="Beam search: the reference's, or the standard prefix beam search (summed alignments, "
+                        "per-token LM term and length bonus)")
+    p.add_argument("--length-bonus", type=float, default=0.0, help="Per-token bonus of --search prefix")
+    p.add_argument("--token-topk", default="auto",
+                   help='Tokens kept per frame by --search prefix: "auto" (max(16, 2 * beam width)) or 1..64')
     p.add_argument("--segment-seconds", type=float, default=None,
                    help="Cut files longer than this at their quietest points and stitch the results (off by default)")
     p.add_argument("--min-segment-seconds", type=float, default=None,
@@ -81,13 +89,15 @@ def main(argv=None) -> int:
         if args.beam_width <= 1 or args.lm_weight <= 0:
             logger.warning("--lm takes effect only with --beam-width > 1 and --lm-weight > 0")
 
+    prefix = dict(search=args.search, length_bonus=args.length_bonus,
+                  token_topk=args.token_topk if args.token_topk == "auto" else int(args.token_topk))
     if args.audio_dir:
         files = find_audio_files(args.audio_dir)
         rows = []
         for path, r in zip(files, transcribe_files(model, files, decoder, args.device, False,
                                                     args.batch_size, args.beam_width, lm=lm,
                                                     lm_weight=args.lm_weight, segment_seconds=args.segment_seconds,
-                                                    min_segment_seconds=args.min_segment_seconds)):
+                                                    min_segment_seconds=args.min_segment_seconds, **prefix)):
             if "error" in r:
                 logger.error(f"Error processing {path}: {r['error']}")
                 rows.append((path.name, f"[ERROR: {r['error']}]"))
@@ -113,7 +123,7 @@ def main(argv=None) -> int:
     preds, refs, paths = [], [], []
     results = transcribe_files(model, [a for a, _ in data], decoder, args.device, False,
                                args.batch_size, args.beam_width, lm=lm, lm_weight=args.lm_weight,
-                               segment_seconds=args.segment_seconds, min_segment_seconds=args.min_segment_seconds)
+                               segment_seconds=args.segment_seconds, min_segment_seconds=args.min_segment_seconds, **prefix)
     for (audio, ref), r in zip(data, results):
         if "error" in r:
             logger.error(f"Error processing {audio}: {r['error']}")

@@ -159,6 +159,12 @@ _SIGNATURES = {
     "vasr_ctc_beam_workspace_elems": ([ctypes.c_int, ctypes.c_int], c_i64),
     "vasr_ctc_beam_shortlist_f32": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 5 + [c_p] * 4 + [c_p], ctypes.c_int),
     "vasr_ctc_beam_search_shortlist": ([c_p, c_p, c_p] + [ctypes.c_int] * 6 + [c_p] * 7 + [c_p], ctypes.c_int),
+    "vasr_ctc_prefix_beam_search": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 5 + [c_p, c_p, c_i64, ctypes.c_double,
+                                                                                ctypes.c_double] + [c_p] * 6 + [c_p],
+                                    ctypes.c_int),
+    "vasr_ctc_prefix_beam_search_shortlist": ([c_p, c_p, c_p] + [ctypes.c_int] * 6 + [c_p, c_p, c_i64, ctypes.c_double,
+                                                                                     ctypes.c_double] + [c_p] * 6 + [c_p],
+                                              ctypes.c_int),
     "vasr_ctc_collapse": ([c_p] + [ctypes.c_int] * 4 + [c_p, c_p, c_p, c_p, c_p], ctypes.c_int),
     "vasr_ctc_emissions_f32": ([c_p, c_i64, c_i64] + [ctypes.c_int] * 3 + [c_p, ctypes.c_int, c_p, c_p, ctypes.c_int,
                                                                           c_p, c_p], ctypes.c_int),

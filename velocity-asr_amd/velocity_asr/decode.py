@@ -9,6 +9,7 @@ Token -> text conversion is host string handling, as in the reference.
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -24,7 +25,7 @@ BLANK_TOKEN = 0
 __all__ = ["BLANK_TOKEN", "DecodingResult", "ctc_greedy_decode", "ctc_greedy_decode_with_timestamps",
            "ctc_beam_search", "ctc_forced_align", "BigramLM", "CTCDecoder", "create_default_vocabulary",
            "greedy_token_ids", "ScoredDecoding", "ctc_greedy_decode_with_confidence", "token_confidences",
-           "AGGREGATIONS"]
+           "AGGREGATIONS", "ctc_prefix_beam_search"]
 
 
 @dataclass
@@ -35,6 +36,7 @@ class DecodingResult:
     tokens: List[int]
     score: float
     timestamps: Optional[List[Tuple[int, int]]] = None
+    logp: Optional[float] = None  # ctc_prefix_beam_search: log p(tokens | frames), all alignments summed
 
 
 def _on_device(logits: torch.Tensor) -> torch.Tensor:
@@ -353,6 +355,132 @@ def _ctc_beam_search_host(logits: torch.Tensor, beam_width: int, blank_token: in
     return all_results
 
 
+def _logaddexp(a: float, b: float) -> float:
+    if a == -math.inf:
+        return b
+    if b == -math.inf:
+        return a
+    m, n = (a, b) if a >= b else (b, a)
+    return m + math.log1p(math.exp(n - m))
+
+
+def ctc_prefix_beam_search(logits: torch.Tensor, beam_width: int = 10, blank_token: int = BLANK_TOKEN,
+                           lm_scorer: Optional[Any] = None, lm_weight: float = 0.0, length_bonus: float = 0.0,
+                           input_lengths=None, token_topk=None) -> List[List[DecodingResult]]:
+    """The standard CTC prefix beam search (extension), where ctc_beam_search is the
+    reference's: every prefix carries the summed probability of ALL its alignments (split into those
+    ending in the blank and in its last token), the language model scores each token once, when it
+    is appended (lm_weight * log p(tok | previous)), and every token earns length_bonus.  Results per
+    utterance, best first: tokens, logp = log p(tokens | frames) and score = (logp + lm_weight *
+    lm_scorer.score(tokens)) + length_bonus * len(tokens), the rank the beam was pruned by.
+
+    Device logits with no scorer or a BigramLM, widths 1..32, run in one launch
+    (vasr_ctc_prefix_beam_search; a row of V <= 16384 log-probabilities lives in LDS).  token_topk = K
+    (1..64) or "auto" (max(16, 2 * beam_width)) prunes every frame to its K most probable non-blank
+    tokens first (vasr_ctc_beam_shortlist_f32, then vasr_ctc_prefix_beam_search_shortlist): the usual
+    token pruning, an approximation with no certificate and no fallback, and open to any vocabulary.
+    Any other scorer, a wider beam, or CPU logits run the same algorithm on the host, with
+    lm_scorer.score(prefix + [tok]) - lm_scorer.score(prefix) as the per-token term."""
+    if logits.dim() != 3:
+        raise ValueError("ctc_prefix_beam_search: logits must be (B, L, V)")
+    W = int(beam_width)
+    if W < 1:
+        raise ValueError(f"ctc_prefix_beam_search: beam_width must be positive, got {beam_width}")
+    lm_on = lm_scorer is not None and lm_weight > 0
+    V = logits.shape[-1]
+    K = None if token_topk is None or V < 2 else beam_shortlist_size(token_topk, V, W)
+    if logits.device.type != "cuda" or (lm_on and not isinstance(lm_scorer, BigramLM)) or W > 32:
+        return _ctc_prefix_beam_search_host(logits, W, blank_token, lm_scorer, lm_weight, length_bonus, input_lengths, K)
+    x = logits.float()
+    kw = dict(frames=input_lengths, lm_table=lm_scorer.device_table(x.device) if lm_on else None,
+              alpha=float(lm_weight) if lm_on else 0.0, beta=float(length_bonus))
+    if K is None:
+        return _prefix_beam_results(*ops.ctc_prefix_beam_search(x, W, blank_token, **kw))
+    kw["frames"] = ops._beam_frames("ctc_prefix_beam_search", input_lengths, x.shape[0], x.shape[1], x.device)
+    short = ops.ctc_beam_shortlist(x, K, blank_token, kw["frames"])
+    return _prefix_beam_results(*ops.ctc_prefix_beam_search_shortlist(*short, V, W, blank_token, **kw))
+
+
+def _prefix_beam_results(toks, lens, scores, logp, nb) -> List[List[DecodingResult]]:
+    toks, lens, scores, logp, nb = (t.cpu().numpy() for t in (toks, lens, scores, logp, nb))
+    return [[DecodingResult(text="", tokens=toks[b, r, :lens[b, r]].tolist(), score=float(scores[b, r]),
+                            logp=float(logp[b, r])) for r in range(int(nb[b]))] for b in range(toks.shape[0])]
+
+
+def _ctc_prefix_beam_search_host(logits: torch.Tensor, beam_width: int, blank_token: int, lm_scorer: Optional[Any],
+                                 lm_weight: float, length_bonus: float, input_lengths=None,
+                                 token_topk: Optional[int] = None) -> List[List[DecodingResult]]:
+    """Host form of ctc_prefix_beam_search, for a Python lm_scorer: float64 over float32
+    log-probabilities.  A beam is (prefix, pb, pnb, S), S the sum of its tokens' language-model terms;
+    contributions are joined by logaddexp in insertion order, one of -inf is not made, and the
+    beam_width keys of largest rank survive, the earlier inserted first among equals (a stable sort
+    over a dict).  token_topk: only each frame's K most probable non-blank tokens (log-probability
+    descending, token ascending) are extended."""
+    B, L, V = logits.shape
+    if input_lengths is None:
+        frames = [L] * B
+    else:
+        counts = input_lengths.tolist() if isinstance(input_lengths, torch.Tensor) else input_lengths
+        frames = [int(n) for n in counts]
+        if len(frames) != B or any(not 0 <= n <= L for n in frames):
+            raise ValueError(f"ctc_prefix_beam_search: input_lengths must be {B} counts in 0..{L}, got {frames}")
+    lm_on = lm_scorer is not None and lm_weight > 0
+    alpha, beta, NEG = float(lm_weight), float(length_bonus), -math.inf
+    all_results = []
+    for b in range(B):
+        log_probs = torch.log_softmax(logits[b, :frames[b]].float(), dim=-1).cpu().numpy()
+        whole: Dict[Tuple[int, ...], float] = {(): lm_scorer.score([]) if lm_on else 0.0}  # scorer's value per prefix
+        beams = [((), 0.0, NEG, 0.0)]
+        for t in range(frames[b]):
+            lp = log_probs[t].tolist()
+            if token_topk is None:
+                tokens = [tok for tok in range(V) if tok != blank_token]
+            else:
+                order = sorted((tok for tok in range(V) if tok != blank_token), key=lambda tok: (-lp[tok], tok))
+                tokens = sorted(order[:token_topk])
+            new: Dict[Tuple[int, ...], List[float]] = {}  # key -> [pb, pnb, S]
+
+            def add(key, which, v, parent, S):
+                if v == NEG:
+                    return
+                e = new.get(key)
+                if e is None:
+                    if lm_on and S is None:  # a new token: the scorer's term for it, once
+                        if key not in whole:
+                            whole[key] = lm_scorer.score(list(key))
+                        S = parent[3] + (whole[key] - whole[parent[0]])
+                    e = new[key] = [NEG, NEG, S if lm_on else 0.0]
+                e[which] = _logaddexp(e[which], v)
+
+            for beam in beams:
+                prefix, pb, pnb, S = beam
+                tot = _logaddexp(pb, pnb)
+                add(prefix, 0, tot + lp[blank_token], beam, S)
+                tail = prefix[-1] if prefix else None
+                for tok in tokens:
+                    if tok == tail:
+                        add(prefix, 1, pnb + lp[tok], beam, S)
+                        add(prefix + (tok,), 1, pb + lp[tok], beam, None)
+                    else:
+                        add(prefix + (tok,), 1, tot + lp[tok], beam, None)
+
+            def rank(kv):
+                key, (pb, pnb, S) = kv
+                s = _logaddexp(pb, pnb)
+                if lm_on:
+                    s = s + alpha * S
+                return s + beta * len(key)
+
+            beams = [(key, e[0], e[1], e[2]) for key, e in sorted(new.items(), key=rank, reverse=True)[:beam_width]]
+        results = []
+        for prefix, pb, pnb, S in beams:
+            logp = _logaddexp(pb, pnb)
+            results.append(DecodingResult(text="", tokens=list(prefix), logp=logp,
+                                          score=((logp + alpha * S) if lm_on else logp) + beta * len(prefix)))
+        all_results.append(results)
+    return all_results
+
+
 def _align_targets(targets, target_lengths, blank_token: int):
     """A list of token lists as a blank-padded (B, Smax) int32 tensor, with its lengths unless given."""
     if not isinstance(targets, torch.Tensor):
@@ -421,6 +549,16 @@ class CTCDecoder:
         beam_results = ctc_beam_search(logits, beam_width=beam_width, blank_token=self.blank_token,
                                        lm_weight=lm_weight, lm_scorer=lm_scorer, input_lengths=input_lengths,
                                        shortlist=shortlist)
+        return self._beam_texts(beam_results, return_all_beams)
+
+    def decode_prefix_beam_search(self, logits: torch.Tensor, beam_width: int = 10, return_all_beams: bool = False, *,
+                                  input_lengths=None, lm_scorer: Optional[Any] = None, lm_weight: float = 0.0,
+                                  length_bonus: float = 0.0, token_topk=None):
+        """decode_beam_search with the standard prefix beam search (ctc_prefix_beam_search): texts, or
+        with return_all_beams the DecodingResults (score = rank, logp = the prefix's log-probability)."""
+        beam_results = ctc_prefix_beam_search(logits, beam_width=beam_width, blank_token=self.blank_token,
+                                              lm_scorer=lm_scorer, lm_weight=lm_weight, length_bonus=length_bonus,
+                                              input_lengths=input_lengths, token_topk=token_topk)
         return self._beam_texts(beam_results, return_all_beams)
 
     def _beam_texts(self, beam_results, return_all_beams: bool):

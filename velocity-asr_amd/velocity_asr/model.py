@@ -199,20 +199,7 @@ class CTCOutputHead(nn.Module):
             V = lin.weight.shape[0]
             K = dec.beam_shortlist_size(shortlist, V, W)
             frames = ops._beam_frames("CTCOutputHead.beam_search", rows, B, L, x.device)
-            xn = ops._ln_prologue(x.reshape(B * L, D), self._ln(normalized))
-            nb = min(B, max(1, int(chunk_bytes) // max(L * V * 4, 1)))
-            buf = torch.empty((nb * L, V), device=x.device, dtype=torch.float32)
-
-            def logits_of(b0: int, b1: int) -> torch.Tensor:
-                return ops.gemm(xn[b0 * L:b1 * L], lin.weight, lin.bias, out=buf[:(b1 - b0) * L]).view(b1 - b0, L, V)
-
-            short = (torch.empty((B, L, K), device=x.device, dtype=torch.int32),
-                     torch.empty((B, L, K), device=x.device, dtype=torch.float32),
-                     torch.empty((B, L), device=x.device, dtype=torch.float32))
-            for b0 in range(0, B, nb):
-                b1 = min(b0 + nb, B)
-                ops.ctc_beam_shortlist(logits_of(b0, b1), K, blank, None if frames is None else frames[b0:b1],
-                                       out=tuple(t[b0:b1] for t in short))
+            short, logits_of = self._shortlists(x, K, blank, frames, chunk_bytes, normalized)
 
             def again(bad, fr):  # an uncertified utterance's own logits, in the same buffer, one at a time
                 parts = [dec._beam_search_exact(logits_of(b, b + 1), W, blank, None if fr is None else fr[i:i + 1])
@@ -220,6 +207,60 @@ class CTCOutputHead(nn.Module):
                 return tuple(torch.cat(p) for p in zip(*parts))
 
             return dec._beam_results(*dec._beam_search_from_shortlist(short, V, W, blank, frames, again))
+
+    def _shortlists(self, x: torch.Tensor, K: int, blank: int, frames, chunk_bytes: int, normalized: bool):
+        """The batch's per-frame shortlists (ops.ctc_beam_shortlist's three (B, L, K) / (B, L) arrays)
+        from the head's input, the (B, L, V) logits existing a chunk of whole utterances at a time in
+        one reused buffer, and logits_of(b0, b1), which forms utterances b0 .. b1 - 1 in that buffer
+        again (rows * V * 4 <= chunk_bytes > 0, at least one utterance).  A fusable() head, under no_grad."""
+        B, L, D = x.shape
+        lin = self.proj[2]
+        V = lin.weight.shape[0]
+        xn = ops._ln_prologue(x.reshape(B * L, D), self._ln(normalized))
+        nb = min(B, max(1, int(chunk_bytes) // max(L * V * 4, 1)))
+        buf = torch.empty((nb * L, V), device=x.device, dtype=torch.float32)
+
+        def logits_of(b0: int, b1: int) -> torch.Tensor:
+            return ops.gemm(xn[b0 * L:b1 * L], lin.weight, lin.bias, out=buf[:(b1 - b0) * L]).view(b1 - b0, L, V)
+
+        short = (torch.empty((B, L, K), device=x.device, dtype=torch.int32),
+                 torch.empty((B, L, K), device=x.device, dtype=torch.float32),
+                 torch.empty((B, L), device=x.device, dtype=torch.float32))
+        for b0 in range(0, B, nb):
+            b1 = min(b0 + nb, B)
+            ops.ctc_beam_shortlist(logits_of(b0, b1), K, blank, None if frames is None else frames[b0:b1],
+                                   out=tuple(t[b0:b1] for t in short))
+        return short, logits_of
+
+    def prefix_beam_search(self, x: torch.Tensor, beam_width: int, blank: int = 0, rows=None, token_topk="auto", lm=None,
+                           lm_weight: float = 0.0, length_bonus: float = 0.0, chunk_bytes: int = 256 << 20,
+                           normalized: bool = False):
+        """decode.ctc_prefix_beam_search(forward(x), beam_width, blank, lm, lm_weight, length_bonus,
+        input_lengths=rows, token_topk=token_topk) without the (B, L, V) logits (extension, DESIGN.md
+        §3.6h): chunked GEMM -> per-frame shortlists as beam_search forms them, then one launch of the
+        pruned standard search, with a decode.BigramLM fused on the device.  token_topk: "auto" or
+        1..64.  A bf16 or QAT head, a one-token vocabulary, token_topk=None, a beam above 32 and any
+        other scorer go through forward()."""
+        from . import decode as dec
+
+        B, L, D = x.shape
+        W = int(beam_width)
+        lin = self.proj[2]
+        lm_on = lm is not None and lm_weight > 0
+        with torch.no_grad():
+            if (token_topk is None or not self.fusable() or lin.weight.shape[0] < 2 or not 1 <= W <= 32
+                    or (lm_on and not isinstance(lm, dec.BigramLM))):
+                return dec.ctc_prefix_beam_search(self.forward(x, normalized=normalized), W, blank, lm, lm_weight,
+                                                  length_bonus, input_lengths=rows, token_topk=token_topk)
+            if int(chunk_bytes) <= 0:
+                raise ValueError("CTCOutputHead.prefix_beam_search: chunk_bytes must be positive")
+            V = lin.weight.shape[0]
+            K = dec.beam_shortlist_size(token_topk, V, W)
+            frames = ops._beam_frames("CTCOutputHead.prefix_beam_search", rows, B, L, x.device)
+            short, _ = self._shortlists(x, K, blank, frames, chunk_bytes, normalized)
+            return dec._prefix_beam_results(*ops.ctc_prefix_beam_search_shortlist(
+                *short, V, W, blank, frames=frames, lm_table=lm.device_table(x.device) if lm_on else None,
+                alpha=float(lm_weight) if lm_on else 0.0, beta=float(length_bonus)))
 
     def fusable(self) -> bool:
         """Whether the loss can run straight from the head's input (ops.ctc_head_emissions): a plain
@@ -407,6 +448,23 @@ class VELOCITYASR(nn.Module):
             _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
             return self.ctc_head.beam_search(x, beam_width, blank, rows=lengths, shortlist=shortlist,
                                              chunk_bytes=chunk_bytes, normalized=normalized)
+
+    def prefix_beam_search(self, mel_spectrogram: torch.Tensor, frames=None, beam_width: int = 10, blank: int = 0,
+                           token_topk="auto", lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0,
+                           chunk_bytes: int = 256 << 20):
+        """The standard CTC prefix beam search (decode.ctc_prefix_beam_search: summed alignments, a
+        per-token language-model term and length bonus) with token pruning, without the (B, L, V)
+        logits (CTCOutputHead.prefix_beam_search): per utterance its beams as DecodingResults with
+        score and logp.  frames: per-utterance mel frame counts of a zero-padded batch."""
+        if mel_spectrogram.device.type != "cuda":
+            _lib.require_device()
+            raise RuntimeError("velocity_asr (MI355X build): prefix_beam_search needs HIP tensors")
+        lengths = self._token_lengths(frames, mel_spectrogram.shape[1])
+        with torch.no_grad():
+            _, x, normalized = self._local_global(mel_spectrogram.to(torch.float32), lengths)
+            return self.ctc_head.prefix_beam_search(x, beam_width, blank, rows=lengths, token_topk=token_topk, lm=lm,
+                                                    lm_weight=lm_weight, length_bonus=length_bonus,
+                                                    chunk_bytes=chunk_bytes, normalized=normalized)
 
     def ctc_loss(self, mel_spectrogram: torch.Tensor, targets: torch.Tensor, input_lengths, target_lengths, *,
                  reduction: str = "mean", zero_infinity: bool = True, frames=None, blank: int = 0) -> torch.Tensor:

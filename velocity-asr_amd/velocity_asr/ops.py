@@ -1880,3 +1880,70 @@ def gemm_ctc_greedy_conf(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.
     (ctc_collapse_slots_conf).  Returns ctc_collapse_conf's tuple (plus (pred, logp) with per_frame)."""
     slots = gemm_argmax_lse(a, w, bias, ln=ln)
     return ctc_collapse_slots_conf(slots, 2 * ((w.shape[0] + 31) // 32), B, blank, frames, per_frame)
+
+
+def _prefix_beam_table(who: str, lm_table, V: int):
+    if lm_table is None:
+        return None
+    _cuda_f32(f"{who}.lm_table", lm_table)
+    if tuple(lm_table.shape) != (V + 1, V):
+        raise ValueError(f"{who}: lm_table must be ({V + 1}, {V}), got {tuple(lm_table.shape)}")
+    return lm_table if lm_table.stride(-1) == 1 else lm_table.contiguous()
+
+
+def ctc_prefix_beam_search(logits: torch.Tensor, beam_width: int, blank: int = 0, *, frames=None, lm_table=None,
+                           alpha: float = 0.0, beta: float = 0.0):
+    """The standard CTC prefix beam search (vasr_ctc_prefix_beam_search) over (B, L, V)
+    logits -> (tokens (B, W, L) int32, lengths (B, W), scores (B, W) float64, log-probabilities (B, W)
+    float64, beams per utterance (B,)), all on the device.  A prefix carries the summed probability of
+    its alignments; score = (logp + alpha * S(prefix)) + beta * len(prefix), S the (V + 1, V) bigram
+    table's score (active when lm_table is given and alpha > 0), each token scored once.  frames as
+    ctc_beam_search.  V <= 16384, beam_width <= 32."""
+    who = "ctc_prefix_beam_search"
+    _cuda_f32(f"{who}.logits", logits)
+    if logits.dim() != 3:
+        raise ValueError(f"{who}: logits must be (B, L, V)")
+    x = logits if logits.stride(-1) == 1 else logits.contiguous()
+    B, Lq, V = x.shape
+    W, dev = int(beam_width), x.device
+    fr = _beam_frames(who, frames, B, Lq, dev)
+    tab = _prefix_beam_table(who, lm_table, V)
+    trie, toks, lens, scores, nbeams = _beam_buffers(B, Lq, W, dev)
+    logp = torch.zeros((B, W), device=dev, dtype=torch.float64)
+    check(L.lib().vasr_ctc_prefix_beam_search(x.data_ptr(), x.stride(1), x.stride(0), B, Lq, V, W, int(blank), ptr(fr),
+                                              ptr(tab), 0 if tab is None else tab.stride(0), float(alpha), float(beta),
+                                              trie.data_ptr(), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                              logp.data_ptr(), nbeams.data_ptr(), stream_of(x)),
+          "vasr_ctc_prefix_beam_search")
+    return toks, lens, scores, logp, nbeams
+
+
+def ctc_prefix_beam_search_shortlist(tok: torch.Tensor, lp: torch.Tensor, blank_lp: torch.Tensor, V: int, beam_width: int,
+                                     blank: int = 0, *, frames=None, lm_table=None, alpha: float = 0.0, beta: float = 0.0):
+    """ctc_prefix_beam_search with token pruning (vasr_ctc_prefix_beam_search_shortlist): the search over
+    ctc_beam_shortlist's arrays, every token outside a frame's K best counting as -inf.  An
+    approximation, without a certificate.  V: the vocabulary size (up to 2^20).  Returns the same five
+    tensors."""
+    who = "ctc_prefix_beam_search_shortlist"
+    _cuda_f32(f"{who}.lp", lp)
+    _cuda_f32(f"{who}.blank_lp", blank_lp)
+    if lp.dim() != 3 or not lp.is_contiguous():
+        raise ValueError(f"{who}: lp must be a contiguous (B, L, K) tensor")
+    B, Lq, K = lp.shape
+    V, W, dev = int(V), int(beam_width), lp.device
+    if (tok.device != dev or tok.dtype != torch.int32 or tok.shape != lp.shape or not tok.is_contiguous()
+            or tuple(blank_lp.shape) != (B, Lq) or not blank_lp.is_contiguous()):
+        raise ValueError(f"{who}: tok must be int32 (B, L, K) and blank_lp (B, L), contiguous, beside lp")
+    if not 1 <= K <= min(BEAM_SHORTLIST_MAX, V - 1):
+        raise ValueError(f"{who}: K = {K} outside 1..{min(BEAM_SHORTLIST_MAX, V - 1)} for V = {V}")
+    fr = _beam_frames(who, frames, B, Lq, dev)
+    tab = _prefix_beam_table(who, lm_table, V)
+    trie, toks, lens, scores, nbeams = _beam_buffers(B, Lq, W, dev)
+    logp = torch.zeros((B, W), device=dev, dtype=torch.float64)
+    check(L.lib().vasr_ctc_prefix_beam_search_shortlist(tok.data_ptr(), lp.data_ptr(), blank_lp.data_ptr(), K, V, B, Lq, W,
+                                                        int(blank), ptr(fr), ptr(tab), 0 if tab is None else tab.stride(0),
+                                                        float(alpha), float(beta), trie.data_ptr(), toks.data_ptr(),
+                                                        lens.data_ptr(), scores.data_ptr(), logp.data_ptr(),
+                                                        nbeams.data_ptr(), stream_of(lp)),
+          "vasr_ctc_prefix_beam_search_shortlist")
+    return toks, lens, scores, logp, nbeams

@@ -91,7 +91,8 @@ def group_words(tokens: Sequence[int], spans: Sequence[Tuple[int, int]], vocabul
 
 def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: bool,
                   beam_width: int = 1, lengths: Optional[List[int]] = None, lm=None,
-                  lm_weight: float = 0.0, confidence: bool = False, raw: bool = False) -> List:
+                  lm_weight: float = 0.0, confidence: bool = False, raw: bool = False, search: str = "reference",
+                  length_bonus: float = 0.0, token_topk="auto") -> List:
     """(b, S) device audio -> [(text, words or None)] through the device pipeline.  lengths:
     per-clip sample counts when the clips were zero-padded to S.  lm / lm_weight: language model
     for the beam search (decode.BigramLM runs on the device).  VASR_BEAM_SHORTLIST=1 (read per call)
@@ -99,11 +100,20 @@ def _decode_batch(model, audio: torch.Tensor, decoder: CTCDecoder, timestamps: b
     from per-frame shortlists, without the (B, L, V) logits.  confidence (greedy only):
     [(text, words with "confidence", path log-probability)] from model.greedy_scored.
     raw: per clip the integer arrays instead of text (a dict as stitch_segments takes and _render
-    turns into the tuple above): what the segments of a long recording are stitched from."""
+    turns into the tuple above): what the segments of a long recording are stitched from.
+    search = "prefix" (beam_width > 1): the standard prefix beam search through
+    model.prefix_beam_search (summed alignments, lm_weight and length_bonus per token, token_topk
+    pruning) instead of the reference's."""
     with torch.no_grad():
         mel = mel_on_device(audio, n_mels=model.config.mel_bins, lengths=lengths,
                             frame_pad=model.temporal_binding.conv_padding())
         frames = None if lengths is None else [n // HOP_LENGTH + 1 for n in lengths]
+        if beam_width > 1 and search == "prefix":
+            beams = model.prefix_beam_search(mel, frames=frames, beam_width=beam_width, blank=decoder.blank_token,
+                                             token_topk=token_topk, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)
+            if raw:
+                return [{"tokens": list(r[0].tokens) if r else []} for r in beams]
+            return [(t, None) for t in decoder._beam_texts(beams, False)]
         if 1 < beam_width <= 32 and not (lm is not None and lm_weight > 0) \
                 and os.environ.get("VASR_BEAM_SHORTLIST", "0") == "1":
             # the same beams without the (B, L, V) logits: per-frame shortlists, then one search launch
@@ -264,9 +274,15 @@ def _resample_group(clips: List[torch.Tensor], sr: int, dev: torch.device) -> Li
 def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timestamps: bool = False,
                      batch_size: int = 16, beam_width: int = 1, lm=None, lm_weight: float = 0.0,
                      confidence: bool = False, segment_seconds: Optional[float] = None,
-                     min_segment_seconds: Optional[float] = None) -> List[Dict]:
+                     min_segment_seconds: Optional[float] = None, search: str = "reference",
+                     length_bonus: float = 0.0, token_topk="auto") -> List[Dict]:
     """Transcribe audio files; returns one result dict per file in input order.  lm / lm_weight:
     language model for beam_width > 1 (a decode.BigramLM is fused on the device).
+    search (extension, beam_width > 1): "reference" is the reference's prefix beam search (best single
+    alignment, the language model's score of the whole prefix added in every frame); "prefix" is the
+    standard one (decode.ctc_prefix_beam_search: alignments summed, lm_weight * log p(tok | previous)
+    and length_bonus once per token), run from per-frame shortlists of token_topk ("auto" or 1..64)
+    tokens without the (B, L, V) logits.  length_bonus and token_topk belong to "prefix" alone.
     confidence (extension, greedy only; implies timestamps): each word also carries
     "confidence" in (0, 1], the minimum over its tokens of the geometric mean of the token's frame
     probabilities, and each result "score", the log-probability of the greedy path.
@@ -286,6 +302,8 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
     """
     if confidence and beam_width > 1:
         raise ValueError("transcribe_files: confidence is reported for greedy decoding (beam_width = 1)")
+    if search not in ("reference", "prefix"):
+        raise ValueError(f'transcribe_files: search must be "reference" or "prefix", got {search!r}')
     timestamps = timestamps or confidence
     seg_max = seg_min = None
     if segment_seconds is not None:
@@ -369,7 +387,8 @@ def transcribe_files(model, paths: Iterable, decoder: CTCDecoder, device, timest
             segmented = any(isinstance(key, tuple) for key, _ in chunk)
             decoded = _decode_batch(model, audio.to(dev), decoder, timestamps, beam_width,
                                     lengths=None if min(ns) == S else ns, lm=lm, lm_weight=lm_weight,
-                                    confidence=confidence, raw=segmented)
+                                    confidence=confidence, raw=segmented, search=search, length_bonus=length_bonus,
+                                    token_topk=token_topk)
             for (i, _), n, dec in zip(chunk, ns, decoded):
                 if isinstance(i, tuple):  # a segment: kept raw until its file is whole
                     seg_raw[i] = dec
