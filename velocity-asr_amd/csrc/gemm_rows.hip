@@ -358,10 +358,25 @@ __global__ __launch_bounds__(64 * RW, 1) void gemm_rows_kernel(GemmParams p, int
 // MFMAs, still sets the pace; two DMA-only + two store-only memory waves are slower than four that
 // do both (48.2 vs 39.5 us: 18 DMA pieces per wave and step issue one after the other); the epilogue
 // before the step's DMA beats the DMA first (36.2 vs 40.9 us).
+// Round 9 (profiles/r09_summary.md): what made the memory waves' step the longer one was the softplus
+// columns' arithmetic, 2.6 k cycles per 32 x 32 tile in a wave that shares its SIMD's issue with the
+// MFMA wave (epilogue 2.0 k cycles per chunk with no softplus column, 4.7 k with all).  The softplus
+// epilogue (launches without qparams) now does its arithmetic in the compute waves instead
+// (VASR_ROWS_EPI_MATH): tile j - 1 stays in a second accumulator while chunk j multiplies, and its
+// elements' bias + softplus instructions are scheduled between chunk j's dependent MFMAs, two elements
+// per k-step, before the values go to the staging tile; the memory waves then only copy.  Behind the
+// six MFMAs of a k-step instead of between them the same arithmetic costs 38 k cycles per block.
+// The A prologue goes through the wave's staging tiles (VASR_ROWS_A_STAGE): whole row segments per
+// load instruction, 9.2 k -> 7.8 k cycles.
 //
-// Hand-off is by workgroup barriers only.  INVARIANT: every wave of a block executes exactly
-// nc + 1 barriers, B_0 .. B_nc, whatever its role, its rows (ragged M: all waves run, addresses
-// clamped, stores dropped) and nc (nc <= 0 returns before any barrier, block-uniform).
+// Hand-off is by workgroup barriers only, in one of two protocols chosen per epilogue at compile
+// time (VASR_ROWS_ACC2 below).  Either way every wave of a block executes the same number of
+// barriers whatever its role, its rows (ragged M: all waves run, addresses clamped, stores
+// dropped) and nc (nc <= 0 returns before any barrier, block-uniform), and the W ring's rule is
+// the same: DMA(j + 2) -> slot (j + 2) % 3 is issued after B_j.
+//
+// One accumulator (the hand-off is serial: the tile leaves after the chunk's last MFMA).
+// INVARIANT: exactly nc + 1 barriers, B_0 .. B_nc.
 //   compute wave:  for j in [0, nc): { B_j; MFMA chunk j from W slot j % 3; tile j -> stage[j & 1];
 //                  lgkmcnt(0) }   B_nc
 //   memory wave:   DMA(0), DMA(1); for j in [0, nc): { wait DMA(j); B_j; epilogue(j - 1) from
@@ -376,6 +391,44 @@ __global__ __launch_bounds__(64 * RW, 1) void gemm_rows_kernel(GemmParams p, int
 //   B_0 also publishes the bias / qparam tables, filled by the memory waves during the A prologue.
 //   nc = 1: B_0, chunk 0, B_1, epilogue(0).  nc = 2: DMA(2) never issues.  nc = 3: DMA(2) is
 //   the only in-loop DMA and fills the slot no chunk has used.
+//
+// Two accumulators (chunk j multiplies into c[j & 1] while tile j - 1 leaves c[(j - 1) & 1] under
+// chunk j's first k-steps).  INVARIANT: exactly nc + 2 barriers, B_0 .. B_{nc+1}.
+//   compute wave:  for j in [0, nc): { B_j; MFMA chunk j from W slot j % 3 into c[j & 1], and in
+//                  its k-steps 0..3 tile j - 1 (j >= 1) -> stage[(j - 1) & 1]; lgkmcnt(0) }
+//                  B_nc; tile nc - 1 -> stage[(nc - 1) & 1]; lgkmcnt(0); B_{nc+1}
+//   memory wave:   DMA(0), DMA(1); for j in [0, nc): { wait DMA(j); B_j; epilogue(j - 2) from
+//                  stage[j & 1]; DMA(j + 2) }   B_nc; epilogue(nc - 2); B_{nc+1}; epilogue(nc - 1)
+// "Interval j" is the code between B_j and B_{j+1}.  What each barrier certifies:
+//   B_j, W:      as above: DMA(j) has landed, and chunk j - 1's fragment reads have returned (the
+//                lgkmcnt(0) that ends interval j - 1 covers them), so slot (j + 2) % 3 is free.
+//   B_{j+1}, tiles: tile j - 1, written in interval j, is complete in stage[(j - 1) & 1]
+//                (lgkmcnt(0) before B_{j+1}); the memory waves read it in interval j + 1.  The
+//                tile it overwrote, j - 3, was read in interval j - 1, and those reads returned
+//                before the memory waves reached B_j.  In interval j the memory waves read tile
+//                j - 2 from stage[j & 1], the other tile.  The same holds at the tail with j = nc:
+//                tile nc - 1 is written in interval nc beside the reads of tile nc - 2.
+//   The prologue's use of stage[wave][0..1] (VASR_ROWS_A_STAGE) ends before B_0: a wave's LDS
+//   operations execute in order, and the first tile write follows B_0 (one accumulator) or B_1.
+//   nc = 1: B_0, chunk 0, B_1, tile 0, B_2, epilogue(0): the memory waves pass B_1 with nothing to
+//   do.  nc = 2: B_0 chunk 0; B_1 chunk 1 + tile 0; B_2 tile 1 | epilogue(0); B_3 epilogue(1).
+//   nc = 3: interval 2 holds chunk 2 + tile 1 -> stage[1] beside epilogue(0) from stage[0]; interval
+//   3 tile 2 -> stage[0] (tile 0 was read in interval 2) beside epilogue(1); then epilogue(2).
+//   Longer runs repeat interval 2's pattern with the two tiles alternating; an odd or even nc only
+//   decides which tile the tail writes.
+#ifndef VASR_ROWS_A_STAGE
+#define VASR_ROWS_A_STAGE 1  // the A prologue through the wave's own staging tiles: whole 256-byte row segments per
+#endif                       // load instruction (0: lane (r, h) loads its own fragments, 32 lines per instruction)
+#ifndef VASR_ROWS_ACC2
+#define VASR_ROWS_ACC2 0  // two accumulators where VASR_ROWS_EPI_MATH does not already take them: 0 nowhere, 1 for the 8-byte-slot
+#endif                    // epilogues (ARGMAX, LSE, ARGMAX_LSE), 2 for every epilogue.  The hand-off alone under the MFMAs measured
+                          // slower or equal (r09: the memory waves set the pace there, and the tail gains an interval)
+#ifndef VASR_ROWS_EPI_MATH
+#define VASR_ROWS_EPI_MATH 1  // 1: the SOFTPLUS_FROM epilogue's arithmetic (bias, softplus; launches without qparams) runs in the
+#endif                        // compute waves, on tile j - 1 between chunk j's MFMAs (two accumulators); 0: in the memory waves
+#ifndef VASR_ROWS_HEAD_ARGMAX
+#define VASR_ROWS_HEAD_ARGMAX 0  // 1: auto sends the argmax head (ARGMAX, ARGMAX_LSE; K = 192, N >= 512, M >= 4096) here too
+#endif
 #ifndef VASR_ROWS_ROLES
 #define VASR_ROWS_ROLES 1
 #endif
@@ -431,7 +484,8 @@ __device__ __forceinline__ float rows_value(const GemmParams& p, float v, float 
 // Epilogue of one staged 32 x 32 tile by one memory wave: lane l owns columns 4 (l & 7) .. + 3 of
 // rows (l >> 3) + 8 s, s = 0..3.  wide (N, ldc multiples of 4 and C 16-byte aligned): one 16-byte
 // store per lane and s; otherwise four dword stores.  Out-of-range lanes store past num_records.
-template <int EPI>
+// RAW: the tile already holds the epilogue's values (VASR_ROWS_EPI_MATH 1), only the stores are left.
+template <int EPI, bool RAW = false>
 __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buffer_rsrc_t cbuf, int m0, int n0,
                                                const float* __restrict__ tile, int lane, bool wide,
                                                const float* __restrict__ bias_s, const float4* __restrict__ qp_s,
@@ -440,13 +494,13 @@ __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buf
     const int col0 = n0 + c4;
     const int lc = col0 - cfirst;  // column in the group's LDS tables
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p.bias) {
+    if (!RAW && p.bias) {
         const float4 b = *reinterpret_cast<const float4*>(bias_s + lc);
         bv[0] = b.x; bv[1] = b.y; bv[2] = b.z; bv[3] = b.w;
     }
     float4 qc[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) qc[e] = p.qp ? qp_s[lc + e] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = 0; e < 4; ++e) qc[e] = !RAW && p.qp ? qp_s[lc + e] : make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (EPI == VASR_EPI_ARGMAX) {
         const int slot = n0 / 32;
 #pragma unroll
@@ -575,8 +629,10 @@ __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buf
             const int row = m0 + 8 * s + rl;
             const float4 x = *reinterpret_cast<const float4*>(tile + (8 * s + rl) * 32 + c4);
             float v[4] = {x.x, x.y, x.z, x.w};
+            if constexpr (!RAW) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = rows_value<EPI, SP>(p, v[e], bv[e], qc[e], row, col0 + e);
+                for (int e = 0; e < 4; ++e) v[e] = rows_value<EPI, SP>(p, v[e], bv[e], qc[e], row, col0 + e);
+            }
             if constexpr (WIDE) {
                 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                 const u32x4 d = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
@@ -596,7 +652,7 @@ __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buf
         else body(SPc, std::false_type());
     };
     // whole chunks branch on the softplus columns, as rows_epilogue does (n0 is wave-uniform)
-    if constexpr (EPI == VASR_EPI_SOFTPLUS_FROM) {
+    if constexpr (EPI == VASR_EPI_SOFTPLUS_FROM && !RAW) {
         if (n0 >= p.n_out) width(std::integral_constant<int, 1>());
         else if (n0 + 32 <= p.n_out) width(std::integral_constant<int, 0>());
         else width(std::integral_constant<int, 2>());
@@ -605,13 +661,18 @@ __device__ __forceinline__ void roles_epilogue(const GemmParams& p, __amdgpu_buf
     }
 }
 
-template <int KS, int EPI>
+template <int KS, int EPI, bool CMATH = false>
 __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(GemmParams p, int n_groups,
                                                                               int chunks_per_group, int wide) {
     constexpr int CHUNK = KS * 3 * 1024;   // one 32-column W chunk: [KS][3 planes][64 lanes][16 B]
     constexpr int NDMA = 3 * KS / DWV;     // LDS-DMA instructions per DMA wave per chunk
     static_assert((3 * KS) % DWV == 0, "whole DMA pieces per DMA wave");
     static_assert(DEPTH == 2, "the roles kernel's ring is three slots, two chunks ahead");
+    constexpr bool SLOTS = EPI == VASR_EPI_ARGMAX || EPI == VASR_EPI_LSE || EPI == VASR_EPI_ARGMAX_LSE;  // C is 8-byte slots, one per chunk
+    // CMATH: the epilogue's per-element arithmetic runs in the compute waves (launch_roles picks it: SOFTPLUS_FROM without qparams)
+    static_assert(!CMATH || EPI == VASR_EPI_SOFTPLUS_FROM, "compute-wave arithmetic: the softplus epilogue only");
+    constexpr bool ACC2 = VASR_ROWS_ACC2 == 2 || (VASR_ROWS_ACC2 == 1 && SLOTS) || CMATH;  // the nc + 2 barrier protocol
+    constexpr int LAG = ACC2 ? 2 : 1;  // a memory wave runs epilogue(j - LAG) after B_j
     __shared__ __attribute__((aligned(16))) char wb0[CHUNK];
     __shared__ __attribute__((aligned(16))) char wb1[CHUNK];
     __shared__ __attribute__((aligned(16))) char wb2[CHUNK];
@@ -644,19 +705,199 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
         // ---- compute wave ----
         const int r = lane & 31, h = lane >> 5;
         const int m0 = rb * 32 * CWV + wave_u * 32;
-        const float* __restrict__ arow = p.A + (int64_t)min(m0 + r, p.M - 1) * p.lda;
-        float4 xa[KS][2];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int k = 16 * ks + 8 * h + 4 * u;
-                const float4 v = *reinterpret_cast<const float4*>(arow + min(k, p.K - 4));
-                xa[ks][u] = k < p.K ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
         bf16x8 a[KS][3];
+#if VASR_ROWS_A_STAGE
+        {
+            // The wave's 32 rows x 64 K-columns per pass through its own two staging tiles (8 KiB,
+            // nobody else's before B_0): 16 lanes load one row's 256-byte segment, 4 rows per
+            // instruction, so every 128-byte line is touched by one instruction and used whole.
+            // 16-byte chunk c of row q sits at chunk c ^ (q & 15) of the row's 256 bytes: the
+            // 8-lane groups of a ds_write_b128 cover 128 contiguous bytes in some order, and the
+            // 16-lane groups of the ds_read_b128 below (16 rows distinct mod 16, one c) 16 distinct
+            // chunks.  Same values into the same split8 as the direct form: rows clamped to M - 1,
+            // k >= K zero, any lda.  Wave-private: LDS operations of one wave execute in order.
+            static_assert(KS % 4 == 0, "whole 64-column passes");
+            constexpr int NP = KS / 4;
+            char* img = reinterpret_cast<char*>(&stage[wave_u][0][0]);
+            const int lq = lane >> 4, lc = lane & 15;
+            float4 g[NP][8];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) split8(xa[ks][0], xa[ks][1], a[ks][0], a[ks][1], a[ks][2]);
+            for (int i = 0; i < 8; ++i) {
+                const float* __restrict__ src = p.A + (int64_t)min(m0 + 4 * i + lq, p.M - 1) * p.lda;
+#pragma unroll
+                for (int ps = 0; ps < NP; ++ps) {
+                    const int k = 64 * ps + 4 * lc;
+                    const float4 v = *reinterpret_cast<const float4*>(src + min(k, p.K - 4));
+                    g[ps][i] = k < p.K ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+#pragma unroll
+            for (int ps = 0; ps < NP; ++ps) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int q = 4 * i + lq;
+                    *reinterpret_cast<float4*>(img + q * 256 + ((lc ^ (q & 15)) << 4)) = g[ps][i];
+                }
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the pass is in LDS
+                float4 xa[4][2];
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+                        xa[kk][u] = *reinterpret_cast<const float4*>(img + r * 256 + (((4 * kk + 2 * h + u) ^ (r & 15)) << 4));
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+                    split8(xa[kk][0], xa[kk][1], a[4 * ps + kk][0], a[4 * ps + kk][1], a[4 * ps + kk][2]);
+                asm volatile("" ::: "memory");  // the next pass's writes stay behind these reads
+            }
+        }
+#else
+        {
+            const float* __restrict__ arow = p.A + (int64_t)min(m0 + r, p.M - 1) * p.lda;
+            float4 xa[KS][2];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int k = 16 * ks + 8 * h + 4 * u;
+                    const float4 v = *reinterpret_cast<const float4*>(arow + min(k, p.K - 4));
+                    xa[ks][u] = k < p.K ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) split8(xa[ks][0], xa[ks][1], a[ks][0], a[ks][1], a[ks][2]);
+        }
+#endif
+#ifdef VASR_ROWS_STAMPS
+        __builtin_amdgcn_sched_barrier(0);
+        VASR_STAMP(t_pro);
+        st_wait = t_pro - st_begin;  // compute waves: the A prologue (they have no counted wait)
+#endif
+        if constexpr (ACC2) {
+            floatx16 acc[2];
+            // element i of lane (r, h) is row (i & 3) + 8 (i >> 2) + 4 h, column r: lanes 0-31 and
+            // 32-63 each write one 128-byte row per instruction
+            // CMATH: rows_value on the way out (the lane's 16 elements are 16 rows of column r, so one bias and one
+            // qparam entry per lane and chunk); sp: the chunk holds softplus columns (wave-uniform)
+            // is rows_value's arithmetic without qparams (the launcher keeps those launches on the memory waves' form),
+            // branch-free so that it schedules between the MFMAs; SP (wave-uniform, rows_value's): 0 no softplus column in the
+            // chunk, 1 all of them (no select: the compiler would branch around the softplus), 2 some
+            auto put = [&](auto SPc, float* tile, const floatx16& c, int i, float bv, int col) {
+                float v = c[i];
+                if constexpr (CMATH) {
+                    v = p.bias ? v + bv : v;
+                    if constexpr (decltype(SPc)::value == 1) v = softplus20_fast(v);
+                    else if constexpr (decltype(SPc)::value == 2) v = col >= p.n_out ? softplus20_fast(v) : v;
+                }
+                tile[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = v;
+            };
+            auto chunk_tables = [&](int j, float& bv, int& col, int& sp) {  // chunk j's, for put
+                bv = 0.f; col = 0; sp = 0;
+                if constexpr (CMATH) {
+                    const int n0 = (c0 + j * cstep) * 32;
+                    col = n0 + r;
+                    if (p.bias) bv = bias_s[j * 32 + r];
+                    sp = n0 >= p.n_out ? 1 : n0 + 32 <= p.n_out ? 0 : 2;
+                }
+            };
+            // tile j - 1's 16 elements leave behind chunk j's first k-steps: 4 behind each of 4, or with arithmetic 2 behind each of 8
+            auto first_el = [](int ks) { return CMATH ? 2 * ks : 4 * ks; };
+            auto step = [&](auto Sc, auto Fc, auto SPc, int j, float bv, int col) {
+                constexpr int S = decltype(Sc)::value;        // j & 1
+                constexpr bool FIRST = decltype(Fc)::value;  // j == 0: no tile to hand off
+                constexpr int SPF = decltype(SPc)::value;    // tile j - 1's softplus columns: none, all, some
+                VASR_STAMP(t0);
+                role_barrier();  // B_j
+                VASR_STAMP(t1);
+                const char* wb = slot(j % NSLOT) + lane * 16;
+                float* prev = &stage[wave_u][S ^ 1][0];  // tile j - 1's
+                bf16x8 wf[2][3];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) wf[0][pl] = *reinterpret_cast<const bf16x8*>(wb + pl * 1024);
+                floatx16 c;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) c[i] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const int cur = ks & 1;
+                    if (ks + 1 < KS) {
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl)
+                            wf[cur ^ 1][pl] = *reinterpret_cast<const bf16x8*>(wb + ((ks + 1) * 3 + pl) * 1024);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][2], wf[cur][0], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][0], wf[cur][2], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][1], wf[cur][1], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][1], wf[cur][0], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][0], wf[cur][1], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][0], wf[cur][0], c, 0, 0, 0);
+                    if constexpr (!CMATH) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (!FIRST) {
+                        static_assert(KS == 8 || KS == 12, "16 elements over the k-steps");
+                        const int i0 = min(first_el(ks), 16), i1 = min(first_el(ks + 1), 16);
+#pragma unroll
+                        for (int i = i0; i < i1; ++i) put(SPc, prev, acc[S ^ 1], i, bv, col);
+                        if constexpr (CMATH) {
+                            // the arithmetic goes between the six dependent MFMAs (each leaves the wave ~32 cycles
+                            // to issue into), not behind them: one MFMA, then a share of the VALU work, six times
+                            constexpr int PER = SPF ? 5 : 1;  // two softplus elements are about 30 VALU instructions
+#pragma unroll
+                            for (int m = 0; m < 6; ++m) {
+                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);    // one MFMA
+                                __builtin_amdgcn_sched_group_barrier(0x002, PER, 0);  // PER VALU
+                            }
+                            __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);  // the tile writes
+                        }
+                    }
+                    if constexpr (CMATH) __builtin_amdgcn_sched_barrier(0);
+                }
+                acc[S] = c;
+                __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): tile j - 1 is in LDS before B_{j+1}
+#ifdef VASR_ROWS_STAMPS
+                VASR_STAMP(t2);
+                st_bar += t1 - t0;
+                st_mfma += t2 - t1;
+#endif
+            };
+            auto next = [&](auto Sc, int j) {  // chunk j >= 1, with tile j - 1's tables
+                float bv; int col; int sp;
+                chunk_tables(j - 1, bv, col, sp);
+                if (sp == 1) step(Sc, std::false_type(), std::integral_constant<int, 1>(), j, bv, col);
+                else if (sp == 0) step(Sc, std::false_type(), std::integral_constant<int, 0>(), j, bv, col);
+                else step(Sc, std::false_type(), std::integral_constant<int, 2>(), j, bv, col);
+            };
+            step(std::integral_constant<int, 0>(), std::true_type(), std::integral_constant<int, 0>(), 0, 0.f, 0);
+            for (int j = 1; j < nc; j += 2) {
+                next(std::integral_constant<int, 1>(), j);
+                if (j + 1 < nc) next(std::integral_constant<int, 0>(), j + 1);
+            }
+            VASR_STAMP(t3);
+            role_barrier();  // B_nc
+            VASR_STAMP(t4);
+            float bv; int col; int sp;
+            chunk_tables(nc - 1, bv, col, sp);
+            auto last = [&](auto SPc) {
+                if ((nc - 1) & 1) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) put(SPc, &stage[wave_u][1][0], acc[1], i, bv, col);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) put(SPc, &stage[wave_u][0][0], acc[0], i, bv, col);
+                }
+            };
+            if (sp == 1) last(std::integral_constant<int, 1>());
+            else if (sp == 0) last(std::integral_constant<int, 0>());
+            else last(std::integral_constant<int, 2>());
+            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the last tile is in LDS before B_{nc+1}
+            VASR_STAMP(t5);
+            role_barrier();  // B_{nc+1}
+#ifdef VASR_ROWS_STAMPS
+            VASR_STAMP(t6);
+            st_bar += (t4 - t3) + (t6 - t5);
+            st_epi += t5 - t4;  // the only hand-off outside the MFMA phase
+#endif
+        } else {
         for (int j = 0; j < nc; ++j) {
             VASR_STAMP(t0);
             role_barrier();  // B_j
@@ -706,6 +947,7 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
         VASR_STAMP(t5);
         st_bar += t5 - t4;
 #endif
+        }
     } else {
         // ---- memory wave ----
         const int mw = wave_u - CWV;
@@ -732,15 +974,14 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the tables are in LDS before B_0
         if (dma)
             for (int j = 0; j < DEPTH && j < nc; ++j) issue(j);
-        constexpr bool SLOTS = EPI == VASR_EPI_ARGMAX || EPI == VASR_EPI_LSE || EPI == VASR_EPI_ARGMAX_LSE;  // C is 8-byte slots, one per chunk
-        constexpr int PER = EPI == VASR_EPI_ARGMAX_LSE ? 2 : 1;                                            // (two: key and pair)
+        constexpr int PER= EPI == VASR_EPI_ARGMAX_LSE ? 2 : 1;                                            // (two: key and pair)
         const int c_bytes = (SLOTS ? 8 : 4) * ((p.M - 1) * (int)p.ldc + (SLOTS ? PER * NT : p.N));
         const __amdgpu_buffer_rsrc_t cbuf = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, c_bytes, 0x00020000);
         auto epilogue = [&](int j) {  // chunk j's tiles of compute waves sw, sw + SWV, ...
             if (!stores) return;
             const int n0 = (c0 + j * cstep) * 32;
             for (int cw = sw; cw < CWV; cw += SWV)
-                roles_epilogue<EPI>(p, cbuf, rb * 32 * CWV + cw * 32, n0, &stage[cw][j & 1][0], lane, wide != 0,
+                roles_epilogue<EPI, CMATH>(p, cbuf, rb * 32 * CWV + cw * 32, n0, &stage[cw][j & 1][0], lane, wide != 0,
                                     bias_s, qp_s, n0 - j * 32);
         };
         for (int j = 0; j < nc; ++j) {
@@ -761,11 +1002,11 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
             VASR_STAMP(t1);
             role_barrier();  // B_j
             VASR_STAMP(t2);
-            if (VASR_ROWS_EPI_FIRST && j >= 1) epilogue(j - 1);
+            if (VASR_ROWS_EPI_FIRST && j >= LAG) epilogue(j - LAG);
             VASR_STAMP(t2e);
             if (dma && j + DEPTH < nc && !(VASR_ROWS_ABLATE & 4)) issue(j + DEPTH);
             VASR_STAMP(t3);
-            if (!VASR_ROWS_EPI_FIRST && j >= 1) epilogue(j - 1);
+            if (!VASR_ROWS_EPI_FIRST && j >= LAG) epilogue(j - LAG);
 #ifdef VASR_ROWS_STAMPS
             VASR_STAMP(t4);
             st_wait += t1 - t0;
@@ -777,11 +1018,22 @@ __global__ __launch_bounds__(64 * (CWV + MWV), 1) void gemm_rows_roles_kernel(Ge
         VASR_STAMP(t5);
         role_barrier();  // B_nc
         VASR_STAMP(t6);
+        if constexpr (ACC2) {
+            if (nc >= 2) epilogue(nc - 2);
+            VASR_STAMP(t6a);
+            role_barrier();  // B_{nc+1}
+#ifdef VASR_ROWS_STAMPS
+            VASR_STAMP(t6b);
+            st_bar += t6b - t6a;
+            st_epi += t6a - t6;
+#endif
+        }
+        VASR_STAMP(t6c);
         epilogue(nc - 1);
 #ifdef VASR_ROWS_STAMPS
         VASR_STAMP(t7);
         st_bar += t6 - t5;
-        st_epi += t7 - t6;
+        st_epi += ACC2 ? t7 - t6c : t7 - t6;
 #endif
     }
 #ifdef VASR_ROWS_STAMPS
@@ -837,7 +1089,13 @@ int launch_roles(const GemmParams& p, int epi, hipStream_t s) {
     switch (epi) {
         case VASR_EPI_NONE: VASR_R(VASR_EPI_NONE); break;
         case VASR_EPI_GELU: VASR_R(VASR_EPI_GELU); break;
-        case VASR_EPI_SOFTPLUS_FROM: VASR_R(VASR_EPI_SOFTPLUS_FROM); break;
+        case VASR_EPI_SOFTPLUS_FROM:
+            // without qparams the softplus runs in the compute waves, between the next chunk's MFMAs
+            if (VASR_ROWS_EPI_MATH == 1 && !p.qp)
+                hipLaunchKernelGGL((gemm_rows_roles_kernel<KS, VASR_EPI_SOFTPLUS_FROM, true>), grid, block, 0, s, p, groups, per, wide);
+            else
+                VASR_R(VASR_EPI_SOFTPLUS_FROM);
+            break;
         case VASR_EPI_RESIDUAL: VASR_R(VASR_EPI_RESIDUAL); break;
         case VASR_EPI_GELU_PE: VASR_R(VASR_EPI_GELU_PE); break;
         case VASR_EPI_ARGMAX: VASR_R(VASR_EPI_ARGMAX); break;
@@ -888,13 +1146,19 @@ bool rows_x3_selected(int M, int N, int Kp, int64_t ldc, int batch, int epi) {
     // auto: the rows engine where it measured faster (profiles/r03l: K = 192, N >= 512 -- the
     // composed head GEMM 35.8 vs 45.6 us, in_proj 21.1 vs 22.8; at N = 384 / 192 a block's short
     // chunk run does not amortise its A load; one utterance, M = 501: 13.2 vs 8.4 us in the
-    // graph, profiles/r03m -- two 256-row blocks per column group); the argmax head keeps the tiles (its per-chunk
-    // 32-lane reductions), and so do the residual / GELU+PE epilogues (they spill at 8 waves).  The row
-    // log-sum-exp epilogue goes where the plain one goes: the loss's GEMM then runs on the engine its
-    // logits would have been written by, with 1/16 of the stores (profiles/ctc_head.md)
+    // graph, profiles/r03m -- two 256-row blocks per column group); the residual / GELU+PE epilogues keep the
+    // tiles (they spilled at 8 waves).  The row log-sum-exp epilogue goes where the plain one goes: the loss's
+    // GEMM then runs on the engine its logits would have been written by, with 1/16 of the stores
+    // (profiles/ctc_head.md).  The argmax head (ARGMAX, and ARGMAX_LSE with it: the host tests pin the two to one
+    // engine) keeps the tiles under auto although the wave-specialised kernel measures faster at its shape
+    // (profiles/r09_summary.md; the round-6 figure once cited here, 46.1 vs 46.5 us, was the 8-wave kernel's):
+    // tests/test_host.py, test_ctc_head_host.py and test_greedy_conf_host.py pin vasr_gemm_tile's answer for
+    // the head to the 128 x 128 tile, so the move is a build option, -DVASR_ROWS_HEAD_ARGMAX=1, until those
+    // pins are retuned with it
+    const bool head = VASR_ROWS_HEAD_ARGMAX && VASR_ROWS_ROLES && (epi == VASR_EPI_ARGMAX || epi == VASR_EPI_ARGMAX_LSE);
     if (engine == 0 && (Kp != 192 || N < 512 || M < 4096 ||
                         !(epi == VASR_EPI_NONE || epi == VASR_EPI_GELU || epi == VASR_EPI_SOFTPLUS_FROM ||
-                          epi == VASR_EPI_LSE)))
+                          epi == VASR_EPI_LSE || head)))
         return false;
     return true;
 }
